@@ -16,7 +16,7 @@ test-gpu:
 	$(PYTHON) -m pytest tests/ -q -m gpu
 
 bench:
-	$(PYTHON) bench.py --steps 30 --warmup 5
+	$(PYTHON) bench.py --steps 30 --warmup 5 --full
 
 doctor:
 	$(PYTHON) -m kata_xpu_device_plugin_amd.tools.doctor

@@ -19,9 +19,15 @@ Scaling mode (driver: torchrun --nproc-per-node N):
   * per-rank work is fixed → "weak" scaling; value = MAX over ranks' p50
     (the whole-job worst-case admission latency).
 
-On a GPU box the run first validates the GPU with the HIP probe suite
-(_gpuprobe: HBM/MFMA/memtest) so the measured control plane corresponds
-to verified silicon; probes are outside the timed region.
+A plain run does only what the headline figure needs: bring the node up,
+warm up, time `--steps` steps, print the result line. `--full` adds the
+side measurements, all outside the timed region: on a GPU box it first
+validates the GPU with the HIP probe suite (_gpuprobe: HBM/MFMA/memtest)
+so the measured control plane corresponds to verified silicon, and it
+measures the no-op RPC floor on the warm channel.
+
+`--dump-outputs DIR` writes what the last timed step returned to its
+caller (see dump_outputs) so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -44,6 +50,12 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pods-per-step", type=int, default=64)
     ap.add_argument("--node-gpus", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (GPU probe "
+                         "validation, no-op RPC floor)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's RPC results to "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -57,6 +69,10 @@ def main() -> int:
 
     if use_cuda:
         torch.cuda.set_device(local_rank % max(1, torch.cuda.device_count()))
+        # Bring the HIP runtime up now: left lazy, its start-up would land
+        # in the pre-timing synchronize, an idle gap between warmup and the
+        # timed steps that lets the daemon and the channel cool down.
+        torch.cuda.synchronize()
 
     if distributed:
         # RCCL needs one GPU per rank; fall back to gloo when testing more
@@ -76,7 +92,7 @@ def main() -> int:
     configure("WARNING")
 
     probe_summary = None
-    if use_cuda and rank == 0:
+    if args.full and use_cuda and rank == 0:
         # Validate the silicon before measuring the control plane (native
         # HIP path must be present on a GPU box — no silent fallback).
         from kata_xpu_device_plugin_amd.health.gpuprobe import probe_device
@@ -155,8 +171,9 @@ def main() -> int:
 
     def admit_one_pod():
         """One pod admission: preferred-allocation then Allocate (the real
-        kubelet flow). Returns (allocate_s, admission_s) — the metric is
-        the Allocate() RPC itself; full admission is reported alongside."""
+        kubelet flow). Returns (allocate_s, admission_s, picked, resp) —
+        the metric is the Allocate() RPC itself; full admission is reported
+        alongside."""
         t0 = time.perf_counter()
         pref = plugin.GetPreferredAllocation(api.PreferredAllocationRequest(
             container_requests=[api.ContainerPreferredAllocationRequest(
@@ -173,18 +190,40 @@ def main() -> int:
         ]))
         t2 = time.perf_counter()
         assert len(resp.container_responses[0].cdi_devices) == gpus_per_pod
-        return t2 - t1, t2 - t0
+        return t2 - t1, t2 - t0, picked, resp
 
     def run_steps(n_steps: int):
-        lat, adm, step_wall = [], [], []
+        lat, adm, step_wall, outs = [], [], [], []
         for _ in range(n_steps):
+            outs = []   # what the caller received in this (→ the last) step
             s0 = time.perf_counter()
             for _ in range(args.pods_per_step):
-                a, full = admit_one_pod()
+                a, full, picked, resp = admit_one_pod()
                 lat.append(a)
                 adm.append(full)
+                outs.append((picked, resp))
             step_wall.append(time.perf_counter() - s0)
-        return lat, adm, step_wall
+        return lat, adm, step_wall, outs
+
+    def dump_outputs(outs, out_dir: str) -> None:
+        """One row per pod admission of the last timed step:
+        picked_device_ids.npy — the device IDs GetPreferredAllocation
+        chose (IOMMU group numbers); allocate_response_bytes.npy — the
+        AllocateResponse in deterministic wire encoding, one byte value
+        per element, rows padded with -1. A few KB; inputs are fixed by
+        the arguments, so equal builds give equal files."""
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        ids = np.array([[int(i) for i in picked] for picked, _ in outs],
+                       dtype=np.float64)
+        wires = [resp.SerializeToString(deterministic=True)
+                 for _, resp in outs]
+        width = max((len(w) for w in wires), default=0)
+        raw = np.full((len(wires), width), -1.0, dtype=np.float32)
+        for row, w in zip(raw, wires):
+            row[:len(w)] = np.frombuffer(w, dtype=np.uint8)
+        np.save(os.path.join(out_dir, "picked_device_ids.npy"), ids)
+        np.save(os.path.join(out_dir, "allocate_response_bytes.npy"), raw)
 
     def barrier_sync():
         if use_cuda:
@@ -197,21 +236,26 @@ def main() -> int:
     # warmup (untimed)
     run_steps(args.warmup)
 
-    # RPC floor: a no-op unary RPC on the same (now warm) channel —
-    # contextualizes how much of the Allocate latency is grpc transport
-    # vs. plugin work.
-    floor = []
-    for _ in range(200):
-        f0 = time.perf_counter()
-        plugin.GetDevicePluginOptions(api.Empty())
-        floor.append(time.perf_counter() - f0)
-    rpc_floor_us = statistics.median(floor) * 1e6
+    rpc_floor_us = None
+    if args.full:
+        # RPC floor: a no-op unary RPC on the same (now warm) channel —
+        # contextualizes how much of the Allocate latency is grpc transport
+        # vs. plugin work.
+        floor = []
+        for _ in range(200):
+            f0 = time.perf_counter()
+            plugin.GetDevicePluginOptions(api.Empty())
+            floor.append(time.perf_counter() - f0)
+        rpc_floor_us = statistics.median(floor) * 1e6
 
     barrier_sync()
     t_start = time.perf_counter()
-    lat, adm, step_wall = run_steps(args.steps)
+    lat, adm, step_wall, last_outs = run_steps(args.steps)
     barrier_sync()
     t_total = time.perf_counter() - t_start
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_outs, args.dump_outputs)
 
     p50_us = statistics.median(lat) * 1e6
     p99_us = statistics.quantiles(lat, n=100)[98] * 1e6 if len(lat) >= 100 else max(lat) * 1e6
@@ -241,11 +285,12 @@ def main() -> int:
             "pods_per_step": args.pods_per_step,
             "concurrent_clients": world_size,
             "admission_p50_us": round(adm_p50_us, 1),  # preferred+allocate
-            "rpc_floor_us": round(rpc_floor_us, 1),    # no-op RPC, same channel
             "p99_us": round(p99_us, 1),
             "pods_per_s_total": round(pods_per_s, 1),
             "parallelism": f"{world_size} churn client(s), one plugin daemon",
         }
+        if rpc_floor_us is not None:   # --full: no-op RPC, same channel
+            config["rpc_floor_us"] = round(rpc_floor_us, 1)
         if probe_summary:
             config["gpu_probe"] = probe_summary
         print(json.dumps({
