@@ -59,6 +59,13 @@ class ProbeReport:
     mfma_f32_ok: bool = False
     mfma_bf16_ok: bool = False
     memtest_mismatches: int = -1
+    # self-checks of what the probes computed (-1 = not run; 0 = healthy)
+    hbm_copy_mismatches: int = -1
+    hbm_chase_mismatches: int = -1
+    lds_mismatches: int = -1
+    mfma_f32_slab_mismatches: int = -1
+    mfma_bf16_slab_mismatches: int = -1
+    bf16_burn_mismatches: int = -1
     passed: bool = False
     failures: List[str] = field(default_factory=list)
 
@@ -97,17 +104,33 @@ def probe_device(
             f"HBM bandwidth {rep.hbm_gbps:.0f} GB/s < floor {hbm_floor_gbps:.0f}"
         )
 
+    rep.hbm_copy_mismatches = int(bw["copy_mismatches"])
+    if rep.hbm_copy_mismatches:
+        rep.failures.append(
+            f"HBM copy: {rep.hbm_copy_mismatches} words of dst differ from src")
+
     lds = g.lds_bandwidth_probe(dev, max(2000, burn_iters))
     rep.lds_tbps = lds["tbps"]
     if is_mi355x and rep.lds_tbps < 80.0:
         rep.failures.append(
             f"LDS bandwidth {rep.lds_tbps:.0f} TB/s < floor 80 (b128 spec ≈150)")
 
+    rep.lds_mismatches = int(lds["mismatches"])
+    if rep.lds_mismatches:
+        rep.failures.append(
+            f"LDS read: {rep.lds_mismatches} lanes summed the wrong slots")
+
     lat = g.hbm_latency_probe(dev, min(bandwidth_bytes, 1 << 30), 500000)
     rep.hbm_latency_ns = lat["latency_ns"]
     if rep.hbm_latency_ns > 1500.0:
         rep.failures.append(
             f"HBM latency {rep.hbm_latency_ns:.0f} ns > 1500 (healthy ≈350)")
+
+    rep.hbm_chase_mismatches = int(lat["final_index"] != lat["expected_index"])
+    if rep.hbm_chase_mismatches:
+        rep.failures.append(
+            f"HBM pointer chase ended at {lat['final_index']}, "
+            f"host walk at {lat['expected_index']}")
 
     pcie = g.pcie_bandwidth_probe(dev, min(bandwidth_bytes, 256 << 20), 5)
     rep.pcie_h2d_gbps = pcie["h2d_gbps"]
@@ -124,6 +147,11 @@ def probe_device(
     if not rep.mfma_f32_ok:
         rep.failures.append(f"f32 MFMA mismatch (max_abs_err={f32['max_abs_err']})")
 
+    rep.mfma_f32_slab_mismatches = int(f32["slab_mismatches"])
+    if rep.mfma_f32_slab_mismatches:
+        rep.failures.append(
+            f"f32 MFMA: {rep.mfma_f32_slab_mismatches} blocks differ from block 0")
+
     bf16 = g.mfma_probe_bf16(dev, burn_iters)
     rep.mfma_bf16_ok = bool(bf16["ok"])
     rep.bf16_tflops = bf16["tflops"]
@@ -133,6 +161,15 @@ def probe_device(
         rep.failures.append(
             f"bf16 MFMA {rep.bf16_tflops:.0f} TFLOP/s < floor {tflops_floor:.0f}"
         )
+
+    rep.mfma_bf16_slab_mismatches = int(bf16["slab_mismatches"])
+    if rep.mfma_bf16_slab_mismatches:
+        rep.failures.append(
+            f"bf16 MFMA: {rep.mfma_bf16_slab_mismatches} blocks differ from block 0")
+    rep.bf16_burn_mismatches = int(bf16["burn_mismatches"])
+    if rep.bf16_burn_mismatches:
+        rep.failures.append(
+            f"bf16 MFMA burn: {rep.bf16_burn_mismatches} lanes differ from wave 0")
 
     mt = g.memtest(dev, memtest_bytes)
     rep.memtest_mismatches = int(mt["mismatches"])

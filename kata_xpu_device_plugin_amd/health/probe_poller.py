@@ -46,7 +46,7 @@ def probe_snapshot(quick_bytes: int = 64 << 20,
             mt = g.memtest(dev, quick_bytes)
             bf16 = g.mfma_probe_bf16(dev, burn_iters)
             out[bdf] = bool(f32["ok"]) and int(mt["mismatches"]) == 0 \
-                and bool(bf16["ok"])
+                and bool(bf16["ok"]) and int(bf16["burn_mismatches"]) == 0
         except Exception as e:
             log.warning("probe of HIP device %d failed: %s", dev, e)
             try:

@@ -9,15 +9,28 @@
 //     instruction — cdna_hip_programming.md §2 coalescing rule), grid ≫256
 //     workgroups to fill all 8 XCDs; a healthy MI355X sustains ≈6.3 TB/s
 //     (MI355X_MICROARCH.md: 8 TB/s peak, 79% achievable).
+//     One pattern-checked copy after timing reports copy_mismatches.
 //   * mfma_probe_f32  : v_mfma_f32_16x16x4_f32 tile with the documented
 //     lane mapping (A[l&15][l>>4], B[l>>4][l&15]; C/D col=l&15,
-//     row=(l>>4)*4+reg — cdna_hip_programming.md §3), verified elementwise
-//     against a host fp32 reference. Exact-f32 MFMA ⇒ bitwise match.
-//   * mfma_probe_bf16 : v_mfma_f32_32x32x16_bf16 throughput burn
-//     (the CDNA4 matrix-core rate, ~2.5 PF dense chip-wide) with a
-//     host-checked numeric result on one tile.
+//     row=(l>>4)*4+reg — cdna_hip_programming.md §3) on full-mantissa
+//     inputs, 2 blocks per CU. Slab 0 must equal the host's k-ordered fmaf
+//     chain bit for bit (measured on MI355X: it does, subnormal products,
+//     inputs and C included) and every other slab must equal slab 0.
+//   * mfma_probe_bf16 : v_mfma_f32_32x32x16_bf16 tile on 2 blocks per CU,
+//     within 16·2^-23·Σ|a·b| of an fp64 reference (the hardware's summation
+//     order is not documented, so no bitwise claim) and bit-identical across
+//     blocks; then a throughput burn (the CDNA4 matrix-core rate, ~2.5 PF
+//     dense chip-wide) whose waves must all agree bit for bit.
+//   * lds_bandwidth_probe : ds_read_b128 streaming; the warm-up launch's
+//     sums are checked exactly, so the reads hit the slots the rate assumes.
+//   * hbm_latency_probe : pointer chase; the final index must equal the
+//     host's walk of the same chain.
 //   * memtest         : address-pattern write/readback over a buffer,
-//     returns mismatch count (catches dead HBM channels).
+//     returns mismatch count (catches dead HBM channels). corrupt_offsets
+//     flips words of the live buffer between write and check, to show the
+//     probe can fail.
+//   * *_run / hbm_copy_check : raw entry points that return what a kernel
+//     computed, for tests against independent references.
 //
 // Wavefront size is 64 everywhere (gfx950; cdna_hip_programming.md §1).
 // Build: hipcc --offload-arch=gfx950 (driven by setup.py / __graft_entry__).
@@ -31,6 +44,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -102,7 +116,13 @@ lds_read_burn(float* __restrict__ out, int iters) {
     // b128 rate (§LDS table). One scalar accumulate per read keeps the
     // loop LDS-bound (8×4 LDS cycles vs 8×2 VALU per batch); the explicit
     // s_waitcnt is mandatory — hipcc pads nothing inside asm (§5.7).
-    unsigned base = (unsigned)(threadIdx.x & 255) * 16u;  // lane-contiguous 16-B slots
+    // The address comes from buf itself and the asm clobbers "memory": with a
+    // bare byte offset and no clobber the compiler sees buf written and never
+    // read, deletes the fill and allocates no LDS at all, and every read
+    // returns 0 from outside the (empty) allocation. Outputs are
+    // early-clobber: the address register is read by all eight instructions.
+    typedef __attribute__((address_space(3))) lds_f32x4 lds_slot;
+    unsigned base = (unsigned)(size_t)(lds_slot*)&buf[threadIdx.x & 255];  // lane-contiguous 16-B slots
     float acc = 0.f;
     for (int it = 0; it < iters; it++) {
         lds_f32x4 v0, v1, v2, v3, v4, v5, v6, v7;
@@ -116,9 +136,10 @@ lds_read_burn(float* __restrict__ out, int iters) {
             "ds_read_b128 %6, %8 offset:24576\n\t"
             "ds_read_b128 %7, %8 offset:28672\n\t"
             "s_waitcnt lgkmcnt(0)"
-            : "=v"(v0), "=v"(v1), "=v"(v2), "=v"(v3),
-              "=v"(v4), "=v"(v5), "=v"(v6), "=v"(v7)
-            : "v"(base));
+            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3),
+              "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
+            : "v"(base)
+            : "memory");
         acc += v0.x + v1.x + v2.x + v3.x + v4.x + v5.x + v6.x + v7.x;
     }
     out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = acc;
@@ -145,17 +166,25 @@ __global__ void pointer_chase(const uint32_t* __restrict__ next,
 // ---------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Every block computes the same tile and stores its own 16×16 slab at
+// D + blockIdx.x*256, so a launch of 2×CUs blocks puts the tile through the
+// matrix cores of every CU and the host can compare the slabs.
 __global__ void mfma_f32_tile(const float* __restrict__ A,  // 16×4 row-major
                               const float* __restrict__ B,  // 4×16 row-major
-                              float* __restrict__ D) {      // 16×16 row-major
+                              const float* __restrict__ C,  // 16×16 or nullptr (= 0)
+                              float* __restrict__ D) {      // gridDim.x × 16×16
     int l = threadIdx.x & (WAVE - 1);
     int row = l & 15, k = l >> 4;
     float a = A[row * 4 + k];
     float b = B[k * 16 + (l & 15)];
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (C) {
+        for (int j = 0; j < 4; j++) acc[j] = C[((l >> 4) * 4 + j) * 16 + (l & 15)];
+    }
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-    if (blockIdx.x == 0 && threadIdx.x < WAVE) {
-        for (int j = 0; j < 4; j++) D[((l >> 4) * 4 + j) * 16 + (l & 15)] = acc[j];
+    if (threadIdx.x < WAVE) {
+        float* slab = D + (size_t)blockIdx.x * 256;
+        for (int j = 0; j < 4; j++) slab[((l >> 4) * 4 + j) * 16 + (l & 15)] = acc[j];
     }
 }
 
@@ -173,7 +202,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ void mfma_bf16_tile(const __bf16* __restrict__ A,  // 32×16 row-major
                                const __bf16* __restrict__ B,  // 16×32 row-major
-                               float* __restrict__ D) {       // 32×32 row-major
+                               float* __restrict__ D) {       // gridDim.x × 32×32
     int l = threadIdx.x & (WAVE - 1);
     int half = l >> 5;          // which 8-wide K slice
     int lane32 = l & 31;
@@ -184,10 +213,11 @@ __global__ void mfma_bf16_tile(const __bf16* __restrict__ A,  // 32×16 row-majo
     }
     f32x16 acc = {};
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-    if (blockIdx.x == 0 && threadIdx.x < WAVE) {
+    if (threadIdx.x < WAVE) {
+        float* slab = D + (size_t)blockIdx.x * 1024;  // one slab per block
         for (int reg = 0; reg < 16; reg++) {
             int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
-            D[row * 32 + lane32] = acc[reg];
+            slab[row * 32 + lane32] = acc[reg];
         }
     }
 }
@@ -220,6 +250,58 @@ mfma_bf16_burn(float* __restrict__ out, int iters) {
 // Host-side wrappers
 // ---------------------------------------------------------------------------
 
+// Argument checks run before the first HIP call of every entry point, so a
+// bad argument is a ValueError on any machine, with or without a GPU.
+void require(bool cond, const char* what) {
+    if (!cond) throw std::invalid_argument(what);
+}
+
+constexpr int MAX_TILE_BLOCKS = 4096;   // 16 MiB of bf16-tile slabs at most
+constexpr int MAX_BURN_BLOCKS = 65536;  // 64 MiB of burn output at most
+
+// Device allocation that is freed on every path, exceptions included.
+struct DevBuf {
+    void* p = nullptr;
+    explicit DevBuf(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+int compute_units(int dev) {
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    return prop.multiProcessorCount;
+}
+
+// A C-contiguous buffer of exactly `count` items of `itemsize` bytes.
+const void* tile_buffer(const py::buffer_info& info, size_t itemsize,
+                        size_t count, const char* what) {
+    bool ok = (size_t)info.itemsize == itemsize && (size_t)info.size == count;
+    py::ssize_t stride = info.itemsize;
+    for (py::ssize_t d = info.ndim - 1; ok && d >= 0; d--) {
+        if (info.shape[d] != 1 && info.strides[d] != stride) ok = false;
+        stride *= info.shape[d];
+    }
+    require(ok, what);
+    return info.ptr;
+}
+
+template <class T>
+py::bytes as_bytes(const std::vector<T>& v) {
+    return py::bytes(reinterpret_cast<const char*>(v.data()), v.size() * sizeof(T));
+}
+
+// Slabs of `slab` floats whose bits differ from slab 0. Every block of a
+// tile launch computes the same thing, so a non-zero count is a sick CU.
+uint64_t slab_mismatches(const std::vector<float>& d, size_t slab) {
+    uint64_t bad = 0;
+    for (size_t s = 1; s * slab < d.size(); s++)
+        if (std::memcmp(d.data() + s * slab, d.data(), slab * sizeof(float)) != 0) bad++;
+    return bad;
+}
+
 int device_count() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -228,6 +310,7 @@ int device_count() {
 }
 
 py::dict device_info(int dev) {
+    require(dev >= 0, "dev must be >= 0");
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     size_t free_b = 0, total_b = 0;
@@ -246,16 +329,53 @@ py::dict device_info(int dev) {
     return d;
 }
 
-py::dict hbm_bandwidth_probe(int dev, size_t bytes, int iters) {
+constexpr uint64_t PATTERN_SALT = 0xA5A5A5A55A5A5A5Aull;
+
+// Pattern-checked copy: fill src with the memtest address pattern, clear dst,
+// run copy_f4 and count the 64-bit words of dst that do not hold the pattern.
+// The pattern differs at every word, so a copy from the wrong index, a
+// skipped element or a short loop bound all show up in the count.
+uint64_t checked_copy(float4* src, float4* dst, size_t n4, int blocks) {
+    size_t n = n4 * 2;  // 64-bit words
+    DevBuf mm(sizeof(unsigned long long));
+    HIP_CHECK(hipMemset(mm.p, 0, sizeof(unsigned long long)));
+    HIP_CHECK(hipMemset(dst, 0, n4 * sizeof(float4)));
+    hipLaunchKernelGGL(pattern_write, dim3(blocks), dim3(256), 0, 0,
+                       (uint64_t*)src, n, PATTERN_SALT);
+    hipLaunchKernelGGL(copy_f4, dim3(blocks), dim3(256), 0, 0, src, dst, n4);
+    hipLaunchKernelGGL(pattern_check, dim3(blocks), dim3(256), 0, 0,
+                       (const uint64_t*)dst, n, PATTERN_SALT,
+                       mm.as<unsigned long long>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    unsigned long long mismatches = 0;
+    HIP_CHECK(hipMemcpy(&mismatches, mm.p, sizeof(mismatches), hipMemcpyDeviceToHost));
+    return mismatches;
+}
+
+py::dict hbm_copy_check(int dev, size_t bytes) {
+    require(dev >= 0, "dev must be >= 0");
+    require(bytes >= sizeof(float4), "bytes must hold at least one float4 (16)");
     HIP_CHECK(hipSetDevice(dev));
     size_t n4 = bytes / sizeof(float4);
-    float4 *src = nullptr, *dst = nullptr;
-    HIP_CHECK(hipMalloc(&src, n4 * sizeof(float4)));
-    HIP_CHECK(hipMalloc(&dst, n4 * sizeof(float4)));
+    int blocks = compute_units(dev) * 8;
+    DevBuf src(n4 * sizeof(float4)), dst(n4 * sizeof(float4));
+    py::dict d;
+    d["mismatches"] = checked_copy(src.as<float4>(), dst.as<float4>(), n4, blocks);
+    d["bytes"] = (uint64_t)(n4 * sizeof(float4));
+    return d;
+}
+
+py::dict hbm_bandwidth_probe(int dev, size_t bytes, int iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(bytes >= sizeof(float4), "bytes must hold at least one float4 (16)");
+    require(iters > 0, "iters must be > 0");
+    HIP_CHECK(hipSetDevice(dev));
+    size_t n4 = bytes / sizeof(float4);
+    DevBuf src_buf(n4 * sizeof(float4)), dst_buf(n4 * sizeof(float4));
+    float4 *src = src_buf.as<float4>(), *dst = dst_buf.as<float4>();
     HIP_CHECK(hipMemset(src, 0x3c, n4 * sizeof(float4)));
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    int blocks = prop.multiProcessorCount * 8;  // ≫256 WGs, fills all XCDs
+    int blocks = compute_units(dev) * 8;  // ≫256 WGs, fills all XCDs
     hipEvent_t t0, t1;
     HIP_CHECK(hipEventCreate(&t0));
     HIP_CHECK(hipEventCreate(&t1));
@@ -274,25 +394,63 @@ py::dict hbm_bandwidth_probe(int dev, size_t bytes, int iters) {
     }
     HIP_CHECK(hipEventDestroy(t0));
     HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(src));
-    HIP_CHECK(hipFree(dst));
+    // one pattern-checked copy after timing: the rate above says nothing
+    // about whether dst ever equalled src
+    uint64_t copy_mismatches = checked_copy(src, dst, n4, blocks);
     double gbps = 2.0 * (double)(n4 * sizeof(float4)) / (best_ms * 1e6);
     py::dict d;
     d["gbps"] = gbps;
     d["best_ms"] = best_ms;
     d["bytes_moved"] = (uint64_t)(2 * n4 * sizeof(float4));
+    d["copy_mismatches"] = copy_mismatches;
     return d;
 }
 
-py::dict lds_bandwidth_probe(int dev, int iters) {
+// lds_read_burn lane t reads slots t, t+256, …, t+1792, whose .x hold their
+// own index, so one iteration adds 8t + 256·(0+…+7) = 8t + 7168. All partial
+// sums are integers; they stay exact in f32 while iters·9208 < 2^24.
+constexpr int LDS_EXACT_ITERS = 1822;
+
+uint64_t lds_mismatches(const std::vector<float>& out, int iters) {
+    uint64_t bad = 0;
+    for (size_t i = 0; i < out.size(); i++)
+        if (out[i] != (float)iters * (float)(8 * (int)(i & 255) + 7168)) bad++;
+    return bad;
+}
+
+int burn_blocks(int dev, int blocks, int per_cu) {
+    return blocks > 0 ? blocks : compute_units(dev) * per_cu;
+}
+
+py::bytes lds_read_burn_run(int dev, int iters, int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(iters > 0, "iters must be > 0");
+    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
     HIP_CHECK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    int blocks = prop.multiProcessorCount * 4;   // 4 × 32 KiB per CU
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, (size_t)blocks * 256 * 4));
+    blocks = burn_blocks(dev, blocks, 4);
+    std::vector<float> h((size_t)blocks * 256);
+    DevBuf out(h.size() * 4);
+    hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out.as<float>(), iters);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
+    return as_bytes(h);
+}
+
+py::dict lds_bandwidth_probe(int dev, int iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(iters > 0, "iters must be > 0");
+    HIP_CHECK(hipSetDevice(dev));
+    int blocks = burn_blocks(dev, 0, 4);   // 4 × 32 KiB per CU
+    std::vector<float> warm((size_t)blocks * 256);
+    DevBuf out_buf(warm.size() * 4);
+    float* out = out_buf.as<float>();
+    static_assert(256 <= LDS_EXACT_ITERS, "warm-up sums must stay exact");
     hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out, 256);
     HIP_CHECK(hipDeviceSynchronize());
+    // the warm-up launch doubles as the read-address check (exact sums)
+    HIP_CHECK(hipMemcpy(warm.data(), out, warm.size() * 4, hipMemcpyDeviceToHost));
+    uint64_t mismatches = lds_mismatches(warm, 256);
     hipEvent_t t0, t1;
     HIP_CHECK(hipEventCreate(&t0));
     HIP_CHECK(hipEventCreate(&t1));
@@ -304,16 +462,21 @@ py::dict lds_bandwidth_probe(int dev, int iters) {
     HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
     HIP_CHECK(hipEventDestroy(t0));
     HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(out));
     // bytes: blocks × 256 lanes × 8 b128-reads × 16 B per iteration
     double bytes = (double)blocks * 256 * 8 * 16 * (double)iters;
     py::dict d;
     d["tbps"] = bytes / (ms * 1e9);
     d["burn_ms"] = ms;
+    d["mismatches"] = mismatches;
     return d;
 }
 
 py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
+    require(dev >= 0, "dev must be >= 0");
+    require(steps > 0, "steps must be > 0");
+    // n >= 2 for the Sattolo loop below; indices are uint32_t
+    require(bytes >= 8, "bytes must hold at least two uint32 (8)");
+    require(bytes / 4 <= ((size_t)1 << 32), "bytes / 4 must not exceed 2^32");
     HIP_CHECK(hipSetDevice(dev));
     size_t n = bytes / sizeof(uint32_t);
     // Sattolo shuffle → one full cycle; stride-randomized to defeat
@@ -328,9 +491,11 @@ py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
     }
     std::vector<uint32_t> next(n);
     for (size_t i = 0; i < n; i++) next[perm[i]] = perm[(i + 1) % n];
-    uint32_t *d_next = nullptr, *d_out = nullptr;
-    HIP_CHECK(hipMalloc(&d_next, n * 4));
-    HIP_CHECK(hipMalloc(&d_out, 4));
+    // the host holds the chain: where `steps` hops from 0 must end
+    uint32_t expected = 0;
+    for (int i = 0; i < steps; i++) expected = next[expected];
+    DevBuf next_buf(n * 4), out_buf(4);
+    uint32_t *d_next = next_buf.as<uint32_t>(), *d_out = out_buf.as<uint32_t>();
     HIP_CHECK(hipMemcpy(d_next, next.data(), n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(pointer_chase, dim3(1), dim3(64), 0, 0, d_next, d_out, 1000);
     HIP_CHECK(hipDeviceSynchronize());
@@ -345,15 +510,20 @@ py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
     HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
     HIP_CHECK(hipEventDestroy(t0));
     HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(d_next));
-    HIP_CHECK(hipFree(d_out));
+    uint32_t final_index = 0;
+    HIP_CHECK(hipMemcpy(&final_index, d_out, 4, hipMemcpyDeviceToHost));
     py::dict d;
     d["latency_ns"] = ms * 1e6 / steps;
     d["steps"] = steps;
+    d["final_index"] = final_index;
+    d["expected_index"] = expected;
     return d;
 }
 
 py::dict pcie_bandwidth_probe(int dev, size_t bytes, int iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(bytes >= 1, "bytes must be >= 1");
+    require(iters > 0, "iters must be > 0");
     // Host-link health: pinned-memory H2D/D2H streaming. MI355X host link
     // is PCIe Gen5 x16 (63 GB/s spec); a degraded link (wrong slot width,
     // retraining) shows up far below that.
@@ -397,136 +567,258 @@ py::dict pcie_bandwidth_probe(int dev, size_t bytes, int iters) {
     return r;
 }
 
-py::dict memtest(int dev, size_t bytes) {
-    HIP_CHECK(hipSetDevice(dev));
+// corrupt_offsets is a test hook that shows the probe can fail: between the
+// write and the check, each listed 64-bit word of the (valid, live) buffer is
+// read back, XORed with corrupt_xor and rewritten with plain hipMemcpy.
+// Offsets outside the buffer are rejected, never accessed.
+py::dict memtest(int dev, size_t bytes, const std::vector<uint64_t>& corrupt_offsets,
+                 uint64_t corrupt_xor) {
+    require(dev >= 0, "dev must be >= 0");
+    require(bytes >= sizeof(uint64_t), "bytes must hold at least one uint64 (8)");
     size_t n = bytes / sizeof(uint64_t);
-    uint64_t* buf = nullptr;
-    unsigned long long* mm = nullptr;
-    HIP_CHECK(hipMalloc(&buf, n * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&mm, sizeof(unsigned long long)));
+    for (uint64_t off : corrupt_offsets)
+        require(off < n, "corrupt_offsets entry is outside the buffer");
+    HIP_CHECK(hipSetDevice(dev));
+    DevBuf buf_mem(n * sizeof(uint64_t)), mm_mem(sizeof(unsigned long long));
+    uint64_t* buf = buf_mem.as<uint64_t>();
+    unsigned long long* mm = mm_mem.as<unsigned long long>();
     HIP_CHECK(hipMemset(mm, 0, sizeof(unsigned long long)));
-    uint64_t salt = 0xA5A5A5A55A5A5A5Aull;
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    int blocks = prop.multiProcessorCount * 8;
+    uint64_t salt = PATTERN_SALT;
+    int blocks = compute_units(dev) * 8;
     hipLaunchKernelGGL(pattern_write, dim3(blocks), dim3(256), 0, 0, buf, n, salt);
+    if (!corrupt_offsets.empty()) {
+        HIP_CHECK(hipDeviceSynchronize());
+        for (uint64_t off : corrupt_offsets) {
+            uint64_t w = 0;
+            HIP_CHECK(hipMemcpy(&w, buf + off, sizeof(w), hipMemcpyDeviceToHost));
+            w ^= corrupt_xor;
+            HIP_CHECK(hipMemcpy(buf + off, &w, sizeof(w), hipMemcpyHostToDevice));
+        }
+    }
     hipLaunchKernelGGL(pattern_check, dim3(blocks), dim3(256), 0, 0, buf, n, salt, mm);
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     unsigned long long mismatches = 0;
     HIP_CHECK(hipMemcpy(&mismatches, mm, sizeof(mismatches), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(buf));
-    HIP_CHECK(hipFree(mm));
     py::dict d;
     d["bytes"] = (uint64_t)(n * sizeof(uint64_t));
     d["mismatches"] = (uint64_t)mismatches;
     return d;
 }
 
-py::dict mfma_probe_f32(int dev) {
+// Deterministic full-mantissa test value: random sign, 23 random mantissa
+// bits, exponent in [-4, 3].
+float lcg_f32(uint64_t& s) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    uint32_t u = (uint32_t)(s >> 63) << 31 |
+                 (uint32_t)(123 + ((s >> 33) & 7)) << 23 |
+                 (uint32_t)((s >> 40) & 0x7fffff);
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+// One launch of mfma_f32_tile on `blocks` blocks → blocks × 256 floats.
+// C may be nullptr (zero accumulator).
+std::vector<float> run_f32_tile(const float* A, const float* B, const float* C,
+                                int blocks) {
+    std::vector<float> hD((size_t)blocks * 256);
+    DevBuf dA(64 * 4), dB(64 * 4), dC(256 * 4), dD(hD.size() * 4);
+    HIP_CHECK(hipMemcpy(dA.p, A, 64 * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dB.p, B, 64 * 4, hipMemcpyHostToDevice));
+    if (C) HIP_CHECK(hipMemcpy(dC.p, C, 256 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mfma_f32_tile, dim3(blocks), dim3(WAVE), 0, 0,
+                       dA.as<float>(), dB.as<float>(),
+                       C ? dC.as<float>() : (const float*)nullptr, dD.as<float>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
+    return hD;
+}
+
+py::bytes mfma_f32_tile_run(int dev, py::buffer A, py::buffer B, py::object C,
+                            int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
+    py::buffer_info ia = A.request(), ib = B.request();
+    const float* pa = (const float*)tile_buffer(ia, 4, 64, "A must be 16x4 contiguous f32");
+    const float* pb = (const float*)tile_buffer(ib, 4, 64, "B must be 4x16 contiguous f32");
+    py::buffer_info ic;
+    const float* pc = nullptr;
+    if (!C.is_none()) {
+        ic = py::cast<py::buffer>(C).request();
+        pc = (const float*)tile_buffer(ic, 4, 256, "C must be 16x16 contiguous f32");
+    }
     HIP_CHECK(hipSetDevice(dev));
-    std::vector<float> hA(16 * 4), hB(4 * 16), hD(16 * 16), ref(16 * 16, 0.f);
-    for (int i = 0; i < 16; i++)
-        for (int k = 0; k < 4; k++) hA[i * 4 + k] = 0.25f * i - 0.5f * k + 0.125f;
-    for (int k = 0; k < 4; k++)
-        for (int j = 0; j < 16; j++) hB[k * 16 + j] = 0.0625f * j + 0.75f * k - 1.f;
-    // asymmetric B so a row/col swap cannot pass (guide §3 note)
+    return as_bytes(run_f32_tile(pa, pb, pc, blocks));
+}
+
+py::dict mfma_probe_f32(int dev) {
+    require(dev >= 0, "dev must be >= 0");
+    HIP_CHECK(hipSetDevice(dev));
+    std::vector<float> hA(16 * 4), hB(4 * 16), ref(16 * 16, 0.f);
+    // Full-mantissa inputs over 8 binades: products and partial sums round at
+    // every step, so only the documented k-ordered fmaf chain reproduces the
+    // bits (dyadic inputs would pass under any order or internal width).
+    uint64_t rng = 0x243F6A8885A308D3ull;
+    for (float& v : hA) v = lcg_f32(rng);
+    for (float& v : hB) v = lcg_f32(rng);
     for (int i = 0; i < 16; i++)
         for (int j = 0; j < 16; j++)
             for (int k = 0; k < 4; k++)
                 ref[i * 16 + j] = fmaf(hA[i * 4 + k], hB[k * 16 + j], ref[i * 16 + j]);
-    float *dA, *dB, *dD;
-    HIP_CHECK(hipMalloc(&dA, hA.size() * 4));
-    HIP_CHECK(hipMalloc(&dB, hB.size() * 4));
-    HIP_CHECK(hipMalloc(&dD, hD.size() * 4));
-    HIP_CHECK(hipMemcpy(dA, hA.data(), hA.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_f32_tile, dim3(1), dim3(WAVE), 0, 0, dA, dB, dD);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD, hD.size() * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(dA)); HIP_CHECK(hipFree(dB)); HIP_CHECK(hipFree(dD));
+    // 2 blocks per CU: every CU's matrix cores run the tile
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    std::vector<float> hD = run_f32_tile(hA.data(), hB.data(), nullptr, blocks);
     double max_abs_err = 0;
-    for (int i = 0; i < 256; i++)
-        max_abs_err = std::max(max_abs_err, (double)std::fabs(hD[i] - ref[i]));
+    for (int i = 0; i < 256; i++) {
+        double e = std::fabs((double)hD[i] - (double)ref[i]);
+        if (std::isnan(e)) { max_abs_err = e; break; }   // std::max would drop it
+        max_abs_err = std::max(max_abs_err, e);
+    }
+    bool bits_equal = std::memcmp(hD.data(), ref.data(), 256 * 4) == 0;
+    uint64_t bad_slabs = slab_mismatches(hD, 256);
     py::dict d;
     d["max_abs_err"] = max_abs_err;   // exact f32 MFMA ⇒ expect 0.0
-    d["ok"] = max_abs_err == 0.0;
+    d["slab_mismatches"] = bad_slabs;
+    d["blocks"] = blocks;
+    d["ok"] = bits_equal && bad_slabs == 0;
     return d;
 }
 
-static float bf16_round(float x) {
-    // emulate bf16 storage rounding (round-to-nearest-even on the top 16 bits)
+static uint16_t bf16_round_bits(float x) {
+    // bf16 storage rounding (round-to-nearest-even on the top 16 bits)
     uint32_t u;
     std::memcpy(&u, &x, 4);
     uint32_t lsb = (u >> 16) & 1u;
     u += 0x7fffu + lsb;
-    u &= 0xffff0000u;
-    float r;
-    std::memcpy(&r, &u, 4);
-    return r;
+    return (uint16_t)(u >> 16);
+}
+
+static float bf16_bits_to_float(uint16_t h) {
+    uint32_t u = (uint32_t)h << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+// One launch of mfma_bf16_tile on `blocks` blocks → blocks × 1024 floats.
+std::vector<float> run_bf16_tile(const uint16_t* A, const uint16_t* B, int blocks) {
+    std::vector<float> hD((size_t)blocks * 1024);
+    DevBuf dA(512 * 2), dB(512 * 2), dD(hD.size() * 4);
+    HIP_CHECK(hipMemcpy(dA.p, A, 512 * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dB.p, B, 512 * 2, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mfma_bf16_tile, dim3(blocks), dim3(WAVE), 0, 0,
+                       dA.as<const __bf16>(), dB.as<const __bf16>(), dD.as<float>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
+    return hD;
+}
+
+py::bytes mfma_bf16_tile_run(int dev, py::buffer A_bits, py::buffer B_bits, int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
+    py::buffer_info ia = A_bits.request(), ib = B_bits.request();
+    const uint16_t* pa = (const uint16_t*)tile_buffer(
+        ia, 2, 512, "A_bits must be 32x16 contiguous uint16");
+    const uint16_t* pb = (const uint16_t*)tile_buffer(
+        ib, 2, 512, "B_bits must be 16x32 contiguous uint16");
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_bf16_tile(pa, pb, blocks));
+}
+
+// Output elements whose bits differ from lane (i & 63) of block 0's wave 0.
+// Every wave of the burn computes the same 64 values.
+uint64_t burn_mismatches(const std::vector<float>& out) {
+    uint64_t bad = 0;
+    for (size_t i = WAVE; i < out.size(); i++)
+        if (std::memcmp(&out[i], &out[i & (WAVE - 1)], 4) != 0) bad++;
+    return bad;
+}
+
+py::dict mfma_bf16_burn_run(int dev, int iters, int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(iters > 0, "iters must be > 0");
+    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
+    HIP_CHECK(hipSetDevice(dev));
+    blocks = burn_blocks(dev, blocks, 2);
+    std::vector<float> h((size_t)blocks * 256);
+    DevBuf out(h.size() * 4);
+    hipLaunchKernelGGL(mfma_bf16_burn, dim3(blocks), dim3(256), 0, 0, out.as<float>(), iters);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
+    py::dict d;
+    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
+    d["mismatches"] = burn_mismatches(h);
+    d["blocks"] = blocks;
+    return d;
 }
 
 py::dict mfma_probe_bf16(int dev, int burn_iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(burn_iters > 0, "burn_iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     // --- correctness tile ---
-    std::vector<float> fA(32 * 16), fB(16 * 32);
-    for (int i = 0; i < 32; i++)
-        for (int k = 0; k < 16; k++) fA[i * 16 + k] = bf16_round(0.03125f * i - 0.0625f * k + 0.5f);
-    for (int k = 0; k < 16; k++)
-        for (int j = 0; j < 32; j++) fB[k * 32 + j] = bf16_round(0.015625f * j + 0.09375f * k - 1.f);
+    // Random bf16 values over 8 binades (all 8 significand bits in play).
+    // Each bf16×bf16 product is exact in f32 and the 16 additions lose at
+    // most one ulp each in any order, so |D − ref| ≤ 16·2^-23·Σ|a·b| holds
+    // for a healthy matrix core whatever its internal summation order; a
+    // mapping error is O(1) relative.
+    uint64_t rng = 0x13198A2E03707344ull;
     std::vector<uint16_t> hA(32 * 16), hB(16 * 32);
-    for (size_t i = 0; i < fA.size(); i++) {
-        uint32_t u; std::memcpy(&u, &fA[i], 4); hA[i] = (uint16_t)(u >> 16);
-    }
-    for (size_t i = 0; i < fB.size(); i++) {
-        uint32_t u; std::memcpy(&u, &fB[i], 4); hB[i] = (uint16_t)(u >> 16);
-    }
-    std::vector<float> ref(32 * 32, 0.f), hD(32 * 32);
-    for (int i = 0; i < 32; i++)
-        for (int j = 0; j < 32; j++)
-            for (int k = 0; k < 16; k++)
-                ref[i * 32 + j] += fA[i * 16 + k] * fB[k * 32 + j];
-    uint16_t *dA, *dB; float* dD;
-    HIP_CHECK(hipMalloc(&dA, hA.size() * 2));
-    HIP_CHECK(hipMalloc(&dB, hB.size() * 2));
-    HIP_CHECK(hipMalloc(&dD, hD.size() * 4));
-    HIP_CHECK(hipMemcpy(dA, hA.data(), hA.size() * 2, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB, hB.data(), hB.size() * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_bf16_tile, dim3(1), dim3(WAVE), 0, 0,
-                       (const __bf16*)dA, (const __bf16*)dB, dD);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD, hD.size() * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(dA)); HIP_CHECK(hipFree(dB)); HIP_CHECK(hipFree(dD));
+    for (uint16_t& v : hA) v = bf16_round_bits(lcg_f32(rng));
+    for (uint16_t& v : hB) v = bf16_round_bits(lcg_f32(rng));
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    std::vector<float> hD = run_bf16_tile(hA.data(), hB.data(), blocks);
     double max_rel_err = 0;
-    for (int i = 0; i < 1024; i++) {
-        double denom = std::max(1.0, (double)std::fabs(ref[i]));
-        max_rel_err = std::max(max_rel_err, (double)std::fabs(hD[i] - ref[i]) / denom);
-    }
+    bool tile_ok = true;
+    for (int i = 0; i < 32; i++)
+        for (int j = 0; j < 32; j++) {
+            double ref = 0, mag = 0;
+            for (int k = 0; k < 16; k++) {
+                double p = (double)bf16_bits_to_float(hA[i * 16 + k]) *
+                           (double)bf16_bits_to_float(hB[k * 32 + j]);
+                ref += p;
+                mag += std::fabs(p);
+            }
+            double err = std::fabs((double)hD[i * 32 + j] - ref);
+            if (!(err <= 16.0 * 0x1p-23 * mag)) tile_ok = false;   // NaN fails
+            if (!std::isnan(max_rel_err)) {
+                double rel = err / std::max(1.0, std::fabs(ref));
+                max_rel_err = std::isnan(rel) ? rel : std::max(max_rel_err, rel);
+            }
+        }
+    uint64_t bad_slabs = slab_mismatches(hD, 1024);
 
     // --- throughput burn ---
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    int blocks = prop.multiProcessorCount * 2;   // 2 × 256-thread WGs per CU
-    float* out;
-    HIP_CHECK(hipMalloc(&out, (size_t)blocks * 256 * 4));
-    hipLaunchKernelGGL(mfma_bf16_burn, dim3(blocks), dim3(256), 0, 0, out, 64);
+    int burn_grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
+    std::vector<float> h_out((size_t)burn_grid * 256);
+    DevBuf out_buf(h_out.size() * 4);
+    float* out = out_buf.as<float>();
+    hipLaunchKernelGGL(mfma_bf16_burn, dim3(burn_grid), dim3(256), 0, 0, out, 64);
     HIP_CHECK(hipDeviceSynchronize());
     hipEvent_t t0, t1;
     HIP_CHECK(hipEventCreate(&t0));
     HIP_CHECK(hipEventCreate(&t1));
     HIP_CHECK(hipEventRecord(t0));
-    hipLaunchKernelGGL(mfma_bf16_burn, dim3(blocks), dim3(256), 0, 0, out, burn_iters);
+    hipLaunchKernelGGL(mfma_bf16_burn, dim3(burn_grid), dim3(256), 0, 0, out, burn_iters);
     HIP_CHECK(hipEventRecord(t1));
     HIP_CHECK(hipEventSynchronize(t1));
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
     HIP_CHECK(hipEventDestroy(t0));
     HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(out));
+    // the timed burn covers every CU; all waves must agree bit for bit
+    HIP_CHECK(hipMemcpy(h_out.data(), out, h_out.size() * 4, hipMemcpyDeviceToHost));
     // FLOPs: blocks × 4 waves/WG × 4 acc × iters × 2·32·32·16
-    double flops = (double)blocks * 4.0 * 4.0 * burn_iters * 2.0 * 32 * 32 * 16;
+    double flops = (double)burn_grid * 4.0 * 4.0 * burn_iters * 2.0 * 32 * 32 * 16;
     py::dict d;
     d["max_rel_err"] = max_rel_err;
-    d["ok"] = max_rel_err < 1e-6;   // exact: inputs are bf16-representable
+    d["slab_mismatches"] = bad_slabs;
+    d["burn_mismatches"] = burn_mismatches(h_out);
+    d["ok"] = tile_ok && bad_slabs == 0;
     d["tflops"] = flops / (ms * 1e9);
     d["burn_ms"] = ms;
     return d;
@@ -540,7 +832,19 @@ PYBIND11_MODULE(_gpuprobe, m) {
     m.def("device_info", &device_info, py::arg("dev") = 0);
     m.def("hbm_bandwidth_probe", &hbm_bandwidth_probe, py::arg("dev") = 0,
           py::arg("bytes") = (size_t)1 << 31, py::arg("iters") = 5);
-    m.def("memtest", &memtest, py::arg("dev") = 0, py::arg("bytes") = (size_t)1 << 31);
+    m.def("memtest", &memtest, py::arg("dev") = 0, py::arg("bytes") = (size_t)1 << 31,
+          py::arg("corrupt_offsets") = std::vector<uint64_t>{},
+          py::arg("corrupt_xor") = (uint64_t)1);
+    m.def("hbm_copy_check", &hbm_copy_check, py::arg("dev") = 0,
+          py::arg("bytes") = (size_t)1 << 28);
+    m.def("lds_read_burn_run", &lds_read_burn_run, py::arg("dev") = 0,
+          py::arg("iters") = 256, py::arg("blocks") = 0);
+    m.def("mfma_f32_tile_run", &mfma_f32_tile_run, py::arg("dev"), py::arg("A"),
+          py::arg("B"), py::arg("C") = py::none(), py::arg("blocks") = 1);
+    m.def("mfma_bf16_tile_run", &mfma_bf16_tile_run, py::arg("dev"),
+          py::arg("A_bits"), py::arg("B_bits"), py::arg("blocks") = 1);
+    m.def("mfma_bf16_burn_run", &mfma_bf16_burn_run, py::arg("dev") = 0,
+          py::arg("iters") = 64, py::arg("blocks") = 0);
     m.def("pcie_bandwidth_probe", &pcie_bandwidth_probe, py::arg("dev") = 0,
           py::arg("bytes") = (size_t)256 << 20, py::arg("iters") = 5);
     m.def("lds_bandwidth_probe", &lds_bandwidth_probe, py::arg("dev") = 0,

@@ -59,6 +59,10 @@ def test_probe_device_report(gp):
                        burn_iters=4000)
     assert rep.passed, rep.failures
     assert "gfx950" in rep.gcn_arch
+    for f in ("memtest_mismatches", "hbm_copy_mismatches", "hbm_chase_mismatches",
+              "lds_mismatches", "mfma_f32_slab_mismatches",
+              "mfma_bf16_slab_mismatches", "bf16_burn_mismatches"):
+        assert getattr(rep, f) == 0, (f, rep.as_dict())
 
 
 def test_live_node_discovery():
