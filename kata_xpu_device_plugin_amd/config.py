@@ -172,6 +172,11 @@ class Config:
     # "auto": use the C++ extension when importable (required on GPU nodes),
     # "require": fail loudly without it, "off": pure-Python (tests only).
     native: str = field(default_factory=lambda: _env("NATIVE", "auto"))
+    # Which gRPC server serves the plugin sockets. "native": the C++
+    # HTTP/2 server in the _native extension (Allocate never enters
+    # Python); "aio": grpc.aio on an asyncio loop (the fallback); "auto":
+    # native when the extension provides it and native != "off".
+    grpc_server: str = field(default_factory=lambda: _env("GRPC_SERVER", "auto"))
 
     def validate(self) -> None:
         if self.device_list_strategy not in STRATEGIES:
@@ -190,6 +195,9 @@ class Config:
             raise ValueError(f"cdi_kind must look like vendor/class, got {self.cdi_kind!r}")
         if self.native not in ("auto", "require", "off"):
             raise ValueError(f"native must be auto|require|off, got {self.native!r}")
+        if self.grpc_server not in ("auto", "native", "aio"):
+            raise ValueError(
+                f"grpc_server must be auto|native|aio, got {self.grpc_server!r}")
         if self.registration_mode not in ("legacy", "watcher", "both"):
             raise ValueError(
                 f"registration_mode must be legacy|watcher|both, "
@@ -214,6 +222,8 @@ class Config:
         g.add_argument("--metrics-port", dest="metrics_port", type=int)
         g.add_argument("--log-level", dest="log_level")
         g.add_argument("--native", dest="native", choices=("auto", "require", "off"))
+        g.add_argument("--grpc-server", dest="grpc_server",
+                       choices=("auto", "native", "aio"))
         g.add_argument("--registration-mode", dest="registration_mode",
                        choices=("legacy", "watcher", "both"))
         g.add_argument("--plugins-registry", dest="plugins_registry_dir")

@@ -24,9 +24,11 @@ Differences from the reference, by design:
 from __future__ import annotations
 
 import asyncio
+import atexit
 import os
 import threading
 import time
+import weakref
 from typing import Dict, List, Optional
 
 import grpc
@@ -54,6 +56,31 @@ ENV_CDI_VENDOR_CLASS = "KUBERNETES_CDI_VENDOR_CLASS"
 # of the PCI_RESOURCE_* convention (reference buildEnv,
 # generic_device_plugin.go:90-96 — dead there, live here).
 ENV_PCI_RESOURCE_PREFIX = "PCI_RESOURCE_"
+
+_DEVICE_PLUGIN_PATH = "/v1beta1.DevicePlugin/"
+
+# Plugins currently served by the native server: its loop thread must be
+# joined before the interpreter is torn down under it.
+_LIVE_NATIVE = weakref.WeakSet()
+
+
+@atexit.register
+def _stop_native_servers() -> None:
+    for plugin in list(_LIVE_NATIVE):
+        srv = plugin._native_server
+        if srv is not None:
+            try:
+                srv.stop(0.0)
+            except Exception:
+                pass
+
+
+def _stream_open() -> None:
+    """DeviceState subscription of one open native ListAndWatch stream."""
+
+
+def native_server_available() -> bool:
+    return _NATIVE is not None and hasattr(_NATIVE, "GrpcServer")
 
 
 class AllocationError(Exception):
@@ -93,10 +120,16 @@ class XPUDevicePlugin:
         self._expected_removals = 0
         self.watcher_servicer = None  # set in watcher registration mode
         self.watcher_socket_path: Optional[str] = None
-        self.allocations = 0          # metrics
-        self.allocate_failures = 0
-        self.last_allocate_s = 0.0
-        self.allocate_seconds_total = 0.0
+        # metrics: Python-side values (aio flavour, and what earlier native
+        # servers of this plugin counted); the properties below add the
+        # running native server's own counters.
+        self._allocations = 0
+        self._allocate_failures = 0
+        self._last_allocate_s = 0.0
+        self._allocate_seconds_total = 0.0
+        self._native_server = None
+        self._native_unsubscribe = None
+        self._stream_subscriptions: List = []
         # hot-path precomputation
         self._devices_dir = os.path.join(cfg.sysfs_root, "bus", "pci", "devices")
         self._vendor_list = list(cfg.vendor_allowlist)
@@ -107,6 +140,44 @@ class XPUDevicePlugin:
                         "loop_lag_us": []} if cfg.rpc_timing_path else None
         self._env_res_name = ENV_PCI_RESOURCE_PREFIX + resource_name.upper(
         ).replace("/", "_").replace(".", "_").replace("-", "_")
+
+    # -- metrics (same names in both server flavours) ---------------------
+    def _native_stats(self):
+        srv = self._native_server
+        return srv.stats() if srv is not None else (0, 0, None, 0.0)
+
+    @property
+    def allocations(self) -> int:
+        return self._allocations + self._native_stats()[0]
+
+    @allocations.setter
+    def allocations(self, v: int) -> None:
+        self._allocations = v
+
+    @property
+    def allocate_failures(self) -> int:
+        return self._allocate_failures + self._native_stats()[1]
+
+    @allocate_failures.setter
+    def allocate_failures(self, v: int) -> None:
+        self._allocate_failures = v
+
+    @property
+    def last_allocate_s(self) -> float:
+        last = self._native_stats()[2]
+        return self._last_allocate_s if not last else last
+
+    @last_allocate_s.setter
+    def last_allocate_s(self, v: float) -> None:
+        self._last_allocate_s = v
+
+    @property
+    def allocate_seconds_total(self) -> float:
+        return self._allocate_seconds_total + self._native_stats()[3]
+
+    @allocate_seconds_total.setter
+    def allocate_seconds_total(self, v: float) -> None:
+        self._allocate_seconds_total = v
 
     def _qn(self, gid: str) -> str:
         qn = self._qn_cache.get(gid)
@@ -123,9 +194,11 @@ class XPUDevicePlugin:
             get_preferred_allocation_available=True,
         )
 
-    def _device_list(self) -> List[object]:
+    def _device_list(self, snapshot=None) -> List[object]:
         devs = []
-        for dev, healthy in self.state.snapshot():
+        if snapshot is None:
+            snapshot = self.state.snapshot()
+        for dev, healthy in snapshot:
             d = api.Device(
                 id=dev.id,
                 health=api.HEALTHY if healthy else api.UNHEALTHY,
@@ -270,6 +343,10 @@ class XPUDevicePlugin:
         return response
 
     async def GetPreferredAllocation(self, request, context):
+        return self._preferred_allocation(request)
+
+    def _preferred_allocation(self, request):
+        """GetPreferredAllocation body, shared by both server flavours."""
         t0 = time.perf_counter() if self._timing is not None else 0.0
         resp = api.PreferredAllocationResponse()
         # gid→BDF map cached per state generation: rebuilt only when the
@@ -305,26 +382,34 @@ class XPUDevicePlugin:
         with self._lifecycle:
             self._start_locked(register)
 
+    def _use_native_server(self) -> bool:
+        """Resolve cfg.grpc_server: "auto" takes the native server whenever
+        the extension provides it (and native != "off"); asking for it
+        explicitly without the extension is an error, not a fallback."""
+        want = self.cfg.grpc_server
+        if want == "aio":
+            return False
+        if native_server_available() and self.cfg.native != "off":
+            return True
+        if want == "native":
+            raise RuntimeError(
+                "grpc_server=native needs the _native extension "
+                "(and native != off)")
+        if self.cfg.native == "require":
+            raise RuntimeError("_native extension required but missing")
+        return False
+
     def _start_locked(self, register: bool) -> None:
-        """Serve with grpc.aio on a dedicated event-loop thread: measured
+        """Serve from the native epoll server when available; otherwise
+        with grpc.aio on a dedicated event-loop thread: measured
         ~3x lower tail latency than the sync ThreadPool server under
         concurrent multi-process kubelet clients (handlers run on the
         loop, no per-call thread handoff)."""
         self._stop.clear()
-        self._loop_ready = threading.Event()
-        self._start_error: Optional[BaseException] = None
-        self._thread = threading.Thread(
-            target=self._serve_thread,
-            name=f"kxdp-grpc-{self.resource_name.split('/')[-1]}",
-            daemon=True,
-        )
-        self._thread.start()
-        if not self._loop_ready.wait(self.cfg.grpc_timeout_s):
-            raise RuntimeError(f"gRPC server for {self.resource_name} "
-                               "did not start in time")
-        if self._start_error is not None:
-            self._thread.join(timeout=2.0)
-            raise self._start_error
+        if self._use_native_server():
+            self._start_native()
+        else:
+            self._start_aio()
         # self-dial until ready (reference waitForGrpcServer :98-105)
         ch = grpc.insecure_channel(f"unix://{self.socket_path}")
         try:
@@ -348,6 +433,164 @@ class XPUDevicePlugin:
         log.info("plugin %s serving on %s (%s registration)",
                  self.resource_name, self.socket_path,
                  self.cfg.registration_mode)
+
+    def _start_aio(self) -> None:
+        self._loop_ready = threading.Event()
+        self._start_error: Optional[BaseException] = None
+        self._thread = threading.Thread(
+            target=self._serve_thread,
+            name=f"kxdp-grpc-{self.resource_name.split('/')[-1]}",
+            daemon=True,
+        )
+        self._thread.start()
+        if not self._loop_ready.wait(self.cfg.grpc_timeout_s):
+            raise RuntimeError(f"gRPC server for {self.resource_name} "
+                               "did not start in time")
+        if self._start_error is not None:
+            self._thread.join(timeout=2.0)
+            raise self._start_error
+
+    # -- native server flavour -------------------------------------------
+    def _start_native(self) -> None:
+        """Same sockets and services as _serve_thread, served by
+        _native.GrpcServer: Allocate, the constant RPCs and ListAndWatch
+        never enter Python; GetPreferredAllocation and the watcher
+        registration service are Python unaries called from its loop."""
+        os.makedirs(self.cfg.kubelet_socket_dir, exist_ok=True)
+        if os.path.exists(self.socket_path):
+            self._note_expected_removal()
+            os.unlink(self.socket_path)
+        paths = [self.socket_path]
+        if self.cfg.registration_mode in ("watcher", "both"):
+            from .watcher_registration import (
+                SERVICE_PATH_PREFIX,
+                WatcherRegistrationServicer,
+            )
+            os.makedirs(self.cfg.plugins_registry_dir, exist_ok=True)
+            self.watcher_servicer = WatcherRegistrationServicer(
+                self.resource_name, self.socket_path)
+            self.watcher_socket_path = os.path.join(
+                self.cfg.plugins_registry_dir, self.socket_name)
+            if os.path.exists(self.watcher_socket_path):
+                os.unlink(self.watcher_socket_path)
+            paths.append(self.watcher_socket_path)
+        srv = _NATIVE.GrpcServer(paths)
+        p = _DEVICE_PLUGIN_PATH
+        srv.register_constant(
+            p + "GetDevicePluginOptions",
+            api.DevicePluginOptions(
+                pre_start_required=False,
+                get_preferred_allocation_available=True,
+            ).SerializeToString())
+        srv.register_constant(
+            p + "PreStartContainer",
+            api.PreStartContainerResponse().SerializeToString())
+        srv.register_watch(p + "ListAndWatch", self._on_watch_streams)
+        srv.register_unary(p + "GetPreferredAllocation",
+                           self._preferred_allocation_bytes)
+        srv.configure_allocate(
+            p + "Allocate",
+            strategy=self.cfg.device_list_strategy,
+            reject_unhealthy=bool(self.cfg.reject_unhealthy),
+            cdi_kind=self.cfg.cdi_kind,
+            env_name=self._env_res_name,
+            dev_root=self.cfg.dev_root,
+            devices_dir=self._devices_dir,
+            vendors=self._vendor_list,
+            required_driver=self.cfg.required_driver,
+            on_reject=self._log_rejection,
+            timing=self._timing is not None,
+        )
+        if self.watcher_servicer is not None and len(paths) > 1:
+            srv.register_unary(SERVICE_PATH_PREFIX + "GetInfo",
+                               self.watcher_servicer.get_info_bytes)
+            srv.register_unary(
+                SERVICE_PATH_PREFIX + "NotifyRegistrationStatus",
+                self.watcher_servicer.notify_registration_status_bytes)
+        self._native_server = srv
+        # Fires once now (initial table + list) and then inside every
+        # set_health()/replace_devices(), under the state lock: when those
+        # return, the next Allocate already sees the new table.
+        self._native_unsubscribe = self.state.subscribe_snapshot(
+            self._push_native_state)
+        try:
+            srv.start()
+        except BaseException:
+            self._native_unsubscribe()
+            self._native_unsubscribe = None
+            self._native_server = None
+            raise
+        _LIVE_NATIVE.add(self)
+
+    def _push_native_state(self, snapshot, generation) -> None:
+        """DeviceState snapshot subscriber — runs under the state lock, so
+        it only uses what it is handed; both native calls are non-blocking
+        pointer swaps."""
+        srv = self._native_server
+        if srv is None:
+            return
+        dev_root = self.cfg.dev_root
+        rows = []
+        for dev, healthy in snapshot:
+            qn = self._qn(dev.id)
+            rows.append((
+                dev.id,
+                [fn.bdf for fn in dev.functions],
+                bool(healthy),
+                api.CDIDevice(name=qn).SerializeToString(),
+                f"{ANNOTATION_PREFIX}vfio{dev.id}",
+                qn,
+                os.path.join(dev_root, dev.vfio_node),
+            ))
+        srv.update_table(rows)
+        srv.publish(api.ListAndWatchResponse(
+            devices=self._device_list(snapshot)).SerializeToString())
+
+    def _on_watch_streams(self, delta: int) -> None:
+        """Every open native ListAndWatch stream holds one DeviceState
+        subscription, released when the stream ends: in both flavours the
+        state's subscriber count is the number of live streams, which is
+        what the subscription-leak test in test_plugin_integration.py
+        checks. Pushes themselves come from _push_native_state, so the
+        subscription's callback has nothing to do."""
+        subs = self._stream_subscriptions
+        for _ in range(delta):
+            subs.append(self.state.subscribe(_stream_open))
+        for _ in range(-delta):
+            if subs:
+                subs.pop()()
+
+    def _preferred_allocation_bytes(self, request: bytes) -> bytes:
+        return self._preferred_allocation(
+            api.PreferredAllocationRequest.FromString(request)
+        ).SerializeToString()
+
+    def _log_rejection(self, err: str) -> None:
+        log.warning("Allocate(%s) rejected: %s", self.resource_name, err)
+
+    def _stop_native(self) -> None:
+        srv = self._native_server
+        if srv is None:
+            return
+        if self._native_unsubscribe is not None:
+            self._native_unsubscribe()
+            self._native_unsubscribe = None
+        srv.stop(1.0)
+        # keep what this server counted across restart()
+        n, fails, last, total = srv.stats()
+        if self._timing is not None:
+            self._timing["allocate_us"] = list(srv.allocate_timing_us())
+            self._timing["loop_lag_us"] = []   # no event loop to lag
+            self._dump_timing()
+        self._native_server = None
+        _LIVE_NATIVE.discard(self)
+        while self._stream_subscriptions:
+            self._stream_subscriptions.pop()()
+        self._allocations += n
+        self._allocate_failures += fails
+        self._allocate_seconds_total += total
+        if last:
+            self._last_allocate_s = last
 
     def _spawn_registration_retry(self) -> None:
         def retry():
@@ -504,6 +747,7 @@ class XPUDevicePlugin:
         # the health watcher doesn't treat it as a kubelet wipe.
         if os.path.exists(self.socket_path):
             self._note_expected_removal()
+        self._stop_native()
         if self._loop is not None and getattr(self, "_stop_async", None) is not None:
             try:
                 self._loop.call_soon_threadsafe(self._stop_async.set)

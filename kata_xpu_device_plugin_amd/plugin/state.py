@@ -31,13 +31,17 @@ class DeviceState:
         self._unhealthy_by: Dict[str, set] = {gid: set() for gid in devices}
         self._watchers: List[queue.Queue] = []
         self._callbacks: List[Callable[[], None]] = []
+        self._snapshot_callbacks: List[Callable[[list, int], None]] = []
         self._generation = 0
 
     # -- snapshots ------------------------------------------------------
+    def _snapshot_locked(self) -> List[Tuple[XPUDevice, bool]]:
+        return [(self._devices[g], not self._unhealthy_by[g])
+                for g in sorted(self._devices, key=_gkey)]
+
     def snapshot(self) -> List[Tuple[XPUDevice, bool]]:
         with self._lock:
-            return [(self._devices[g], not self._unhealthy_by[g])
-                    for g in sorted(self._devices, key=_gkey)]
+            return self._snapshot_locked()
 
     def device(self, gid: str) -> Optional[XPUDevice]:
         with self._lock:
@@ -100,7 +104,14 @@ class DeviceState:
             self._generation += 1
             self._notify_locked()
 
-    def _notify_locked(self) -> None:
+    def _notify_locked(self, changed: bool = True) -> None:
+        if changed and self._snapshot_callbacks:
+            snap = self._snapshot_locked()
+            for scb in self._snapshot_callbacks:
+                try:
+                    scb(snap, self._generation)
+                except Exception:
+                    log.exception("state snapshot subscriber failed")
         for q in self._watchers:
             try:
                 q.put_nowait(self._generation)
@@ -143,12 +154,34 @@ class DeviceState:
                     pass
         return unsubscribe
 
+    def subscribe_snapshot(
+        self, cb: Callable[[List[Tuple[XPUDevice, bool]], int], None],
+    ) -> Callable[[], None]:
+        """Register ``cb(snapshot, generation)``, fired once now and then
+        after every effective change (not on poke()) — always UNDER the
+        state lock, with the snapshot built under that same lock. So when
+        set_health()/replace_devices() returns, every subscriber has
+        already been handed the new state. The callback must not block and
+        must not call back into this object (the lock is not reentrant).
+        Returns an idempotent unsubscriber."""
+        with self._lock:
+            self._snapshot_callbacks.append(cb)
+            cb(self._snapshot_locked(), self._generation)
+
+        def unsubscribe() -> None:
+            with self._lock:
+                try:
+                    self._snapshot_callbacks.remove(cb)
+                except ValueError:
+                    pass
+        return unsubscribe
+
     def poke(self) -> None:
         """Wake all watchers without a state change (shutdown path: lets
         event-driven streams observe their stop flag immediately instead of
         waiting out the gRPC shutdown grace)."""
         with self._lock:
-            self._notify_locked()
+            self._notify_locked(changed=False)
 
 
 def _gkey(g: str):

@@ -83,7 +83,7 @@ class WatcherRegistrationServicer:
         self.versions = list(versions)
         self.last_status = None
 
-    async def GetInfo(self, request, context):
+    def get_info(self):
         return PluginInfo(
             type=DEVICE_PLUGIN_TYPE,
             name=self.resource_name,
@@ -91,7 +91,13 @@ class WatcherRegistrationServicer:
             supported_versions=self.versions,
         )
 
+    async def GetInfo(self, request, context):
+        return self.get_info()
+
     async def NotifyRegistrationStatus(self, request, context):
+        return self.notify_registration_status(request)
+
+    def notify_registration_status(self, request):
         self.last_status = (request.plugin_registered, request.error)
         if request.plugin_registered:
             log.info("kubelet accepted plugin %s (watcher mode)", self.resource_name)
@@ -99,6 +105,18 @@ class WatcherRegistrationServicer:
             log.error("kubelet REJECTED plugin %s: %s",
                       self.resource_name, request.error)
         return RegistrationStatusResponse()
+
+    # bytes-in/bytes-out forms for the native server's register_unary()
+    def get_info_bytes(self, request: bytes) -> bytes:
+        InfoRequest.FromString(request)
+        return self.get_info().SerializeToString()
+
+    def notify_registration_status_bytes(self, request: bytes) -> bytes:
+        return self.notify_registration_status(
+            RegistrationStatus.FromString(request)).SerializeToString()
+
+
+SERVICE_PATH_PREFIX = "/pluginregistration.Registration/"
 
 
 def add_watcher_registration_servicer(server: grpc.Server, servicer) -> None:

@@ -520,6 +520,9 @@ std::vector<std::string> select_preferred(
 
 }  // namespace
 
+// native/xpu_grpc_server.cpp: the GrpcServer class
+void kxdp_init_grpc_server(py::module_& m);
+
 PYBIND11_MODULE(_native, m) {
     m.doc() = "Native fast paths for kata-xpu-device-plugin-amd";
     m.def("scan_pci", &scan_pci, py::arg("devices_dir"), py::arg("vendors"),
@@ -534,4 +537,5 @@ PYBIND11_MODULE(_native, m) {
     m.def("select_preferred", &select_preferred, py::arg("locality"),
           py::arg("available"), py::arg("must_include"), py::arg("size"),
           "Exact xGMI/NUMA bucket-composition preferred-set selection");
+    kxdp_init_grpc_server(m);
 }

@@ -77,9 +77,13 @@ if __name__ == "__main__" or "setuptools" in sys.modules:
             ext_modules=[
                 Extension(
                     f"{PKG}._native",
-                    sources=["native/xpu_native.cpp"],
-                    include_dirs=[pybind11.get_include()],
+                    sources=["native/xpu_native.cpp",
+                             "native/xpu_grpc_server.cpp"],
+                    depends=["native/h2.h", "native/hpack.h",
+                             "native/pbwire.h"],
+                    include_dirs=[pybind11.get_include(), "native"],
                     extra_compile_args=["-O2", "-std=c++17"],
+                    extra_link_args=["-pthread"],
                     language="c++",
                 ),
             ],
