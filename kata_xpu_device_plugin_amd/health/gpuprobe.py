@@ -30,6 +30,11 @@ log = get_logger(__name__)
 HBM_GBPS_FLOOR_MI355X = 4000.0
 BF16_TFLOPS_FLOOR_MI355X = 1000.0
 PCIE_GBPS_FLOOR = 20.0  # Gen5 x16 is ~63 GB/s; below 20 = degraded link
+# Block-scaled MX burns (profiles/mfma_lowp.md): the smaller of 0.4× the
+# guide's peak (~5 PF MX-fp8, ~10 PF MX-fp4) and 0.5× the measured median
+# (4320 and 8237 TF).
+MX_FP8_TFLOPS_FLOOR_MI355X = 2000.0
+MX_FP4_TFLOPS_FLOOR_MI355X = 4000.0
 
 
 def _ext():
@@ -66,6 +71,17 @@ class ProbeReport:
     mfma_f32_slab_mismatches: int = -1
     mfma_bf16_slab_mismatches: int = -1
     bf16_burn_mismatches: int = -1
+    # low-precision matrix-core probes (probe_device(low_precision=True))
+    mfma_fp8_ok: bool = False
+    mfma_mx_fp8_ok: bool = False
+    mfma_mx_fp4_ok: bool = False
+    mx_fp8_tflops: float = 0.0
+    mx_fp4_tflops: float = 0.0
+    mfma_fp8_slab_mismatches: int = -1
+    mfma_mx_fp8_slab_mismatches: int = -1
+    mfma_mx_fp4_slab_mismatches: int = -1
+    mx_fp8_burn_mismatches: int = -1
+    mx_fp4_burn_mismatches: int = -1
     passed: bool = False
     failures: List[str] = field(default_factory=list)
 
@@ -80,9 +96,15 @@ def probe_device(
     burn_iters: int = 20000,
     hbm_floor_gbps: Optional[float] = None,
     tflops_floor: Optional[float] = None,
+    low_precision: bool = False,
+    fp8_tflops_floor: Optional[float] = None,
+    fp4_tflops_floor: Optional[float] = None,
 ) -> ProbeReport:
     """Run the full probe suite on one GPU; raises only on infrastructure
-    errors — a sick GPU yields passed=False with reasons."""
+    errors — a sick GPU yields passed=False with reasons.
+
+    `low_precision=True` adds the FP8 and block-scaled MX (FP8/FP4)
+    matrix-core probes; they exist on gfx950 only."""
     g = _ext()
     rep = ProbeReport(device=dev)
     info = g.device_info(dev)
@@ -171,6 +193,10 @@ def probe_device(
         rep.failures.append(
             f"bf16 MFMA burn: {rep.bf16_burn_mismatches} lanes differ from wave 0")
 
+    if low_precision:
+        _probe_low_precision(g, rep, dev, burn_iters, is_mi355x,
+                             fp8_tflops_floor, fp4_tflops_floor)
+
     mt = g.memtest(dev, memtest_bytes)
     rep.memtest_mismatches = int(mt["mismatches"])
     if rep.memtest_mismatches:
@@ -186,6 +212,44 @@ def probe_device(
         "PASS" if rep.passed else rep.failures,
     )
     return rep
+
+
+def _probe_low_precision(g, rep: ProbeReport, dev: int, burn_iters: int,
+                         is_mi355x: bool, fp8_tflops_floor: Optional[float],
+                         fp4_tflops_floor: Optional[float]) -> None:
+    """FP8 / MX-fp8 / MX-fp4 tiles and MX burns; one failure per failed check."""
+    if not is_mi355x:
+        # v_mfma_*_fp8 (OCP) and v_mfma_scale_* do not exist elsewhere
+        rep.failures.append(
+            f"low-precision MFMA probes skipped: {rep.gcn_arch or 'unknown arch'} "
+            "is not gfx950")
+        return
+    if fp8_tflops_floor is None:
+        fp8_tflops_floor = MX_FP8_TFLOPS_FLOOR_MI355X
+    if fp4_tflops_floor is None:
+        fp4_tflops_floor = MX_FP4_TFLOPS_FLOOR_MI355X
+    lp = g.mfma_probe_lowp(dev, burn_iters)
+    for label, key in (("fp8", "fp8"), ("MX-fp8", "mx_fp8"), ("MX-fp4", "mx_fp4")):
+        ok = bool(lp[f"{key}_ok"])
+        slabs = int(lp[f"{key}_slab_mismatches"])
+        setattr(rep, f"mfma_{key}_ok", ok)
+        setattr(rep, f"mfma_{key}_slab_mismatches", slabs)
+        if not ok:
+            rep.failures.append(
+                f"{label} MFMA mismatch (exact tile differs from the host product)")
+        if slabs:
+            rep.failures.append(f"{label} MFMA: {slabs} blocks differ from block 0")
+    for label, key, floor in (("MX-fp8", "mx_fp8", fp8_tflops_floor),
+                              ("MX-fp4", "mx_fp4", fp4_tflops_floor)):
+        tflops = float(lp[f"{key}_tflops"])
+        burn = int(lp[f"{key}_burn_mismatches"])
+        setattr(rep, f"{key}_tflops", tflops)
+        setattr(rep, f"{key}_burn_mismatches", burn)
+        if burn:
+            rep.failures.append(f"{label} MFMA burn: {burn} lanes differ from wave 0")
+        if tflops < floor:
+            rep.failures.append(
+                f"{label} MFMA {tflops:.0f} TFLOP/s < floor {floor:.0f}")
 
 
 def _probe_as_dict(dev: int, kw: Dict) -> Dict:

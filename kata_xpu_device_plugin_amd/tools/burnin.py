@@ -1,6 +1,6 @@
 """GPU burn-in CLI: validate every visible GPU before vfio binding.
 
-    python -m kata_xpu_device_plugin_amd.tools.burnin [--json] [--quick]
+    python -m kata_xpu_device_plugin_amd.tools.burnin [--json] [--quick] [--low-precision]
 
 Exit code 0 iff every GPU passes. See health/gpuprobe.py for the probes.
 """
@@ -19,6 +19,9 @@ def main(argv=None) -> int:
     p.add_argument("--json", action="store_true", help="machine-readable output")
     p.add_argument("--quick", action="store_true",
                    help="small buffers / short burn (smoke, not soak)")
+    p.add_argument("--low-precision", action="store_true",
+                   help="also probe the FP8 and block-scaled MX (FP8/FP4) "
+                        "matrix-core paths (gfx950 only)")
     p.add_argument("--bandwidth-gib", type=float, default=2.0)
     p.add_argument("--memtest-gib", type=float, default=2.0)
     p.add_argument("--parallel", action="store_true",
@@ -37,6 +40,8 @@ def main(argv=None) -> int:
             bandwidth_bytes=int(args.bandwidth_gib * (1 << 30)),
             memtest_bytes=int(args.memtest_gib * (1 << 30)),
         )
+    if args.low_precision:
+        kw["low_precision"] = True
     if args.soak_minutes > 0:
         import time
         deadline = time.monotonic() + args.soak_minutes * 60

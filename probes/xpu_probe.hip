@@ -21,6 +21,14 @@
 //     order is not documented, so no bitwise claim) and bit-identical across
 //     blocks; then a throughput burn (the CDNA4 matrix-core rate, ~2.5 PF
 //     dense chip-wide) whose waves must all agree bit for bit.
+//   * mfma_probe_lowp : the low-precision matrix-core paths tenants buy the
+//     part for. v_mfma_f32_16x16x32_fp8_fp8 and the CDNA4-only
+//     v_mfma_scale_f32_16x16x128_f8f6f4 (OCP e4m3 and e2m1 operands, E8M0
+//     block scales) each run a fixed tile whose fp64 product is exact in f32
+//     under any summation order, on 2 blocks per CU: slab 0 bitwise against
+//     the host, every slab bitwise against slab 0. Then an MX-fp8 and an
+//     MX-fp4 throughput burn (~5 PF and ~10 PF dense chip-wide) whose waves
+//     must all agree bit for bit. FP6 is not probed (FP4's datapath and rate).
 //   * lds_bandwidth_probe : ds_read_b128 streaming; the warm-up launch's
 //     sums are checked exactly, so the reads hit the slots the rate assumes.
 //   * hbm_latency_probe : pointer chase; the final index must equal the
@@ -243,6 +251,150 @@ mfma_bf16_burn(float* __restrict__ out, int iters) {
     float s = 0;
     for (int r = 0; r < 16; r++) s += acc0[r] + acc1[r] + acc2[r] + acc3[r];
     // one store per lane; never zero, so the compiler cannot DCE the loop
+    out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+// ---------------------------------------------------------------------------
+// FP8 and block-scaled MX (FP8/FP4) MFMA. Operands arrive as row-major element
+// codes, one uint8 per element; the kernels do the lane packing, so the lane
+// maps below are the ones tests/test_gpu_lowp_kernels.py pins on hardware
+// (decode sweep, one-k-at-a-time identity, scale map).
+//
+// Format numbers are the instruction's own cbsz (A) / blgp (B) encodings.
+// FP6 (e2m3 = 2, e3m2 = 3) needs 6-bit packing and runs at the FP4 rate on
+// the same datapath; it is out of scope here.
+// ---------------------------------------------------------------------------
+constexpr int FMT_E4M3 = 0, FMT_E5M2 = 1, FMT_E2M1 = 4;
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// v_mfma_f32_16x16x32_{fp8,bf8}_{fp8,bf8}: lane l holds A[l&15][8(l>>4)+j]
+// and B[8(l>>4)+j][l&15] in byte j of its 64-bit operand; C/D as every other
+// 16×16 form (col = l&15, row = 4(l>>4)+reg).
+template <int AF, int BF>
+__global__ void mfma_fp8_tile(const uint8_t* __restrict__ A,  // 16×32 codes
+                              const uint8_t* __restrict__ B,  // 32×16 codes
+                              float* __restrict__ D) {        // gridDim.x × 16×16
+    int l = threadIdx.x & (WAVE - 1);
+    int rc = l & 15, g = l >> 4;
+    uint64_t a = 0, b = 0;
+    for (int j = 0; j < 8; j++) {
+        a |= (uint64_t)A[rc * 32 + 8 * g + j] << (8 * j);
+        b |= (uint64_t)B[(8 * g + j) * 16 + rc] << (8 * j);
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (AF == FMT_E4M3 && BF == FMT_E4M3)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
+    else if constexpr (AF == FMT_E4M3)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_bf8((long)a, (long)b, acc, 0, 0, 0);
+    else if constexpr (BF == FMT_E4M3)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_fp8((long)a, (long)b, acc, 0, 0, 0);
+    else
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)a, (long)b, acc, 0, 0, 0);
+    float* slab = D + (size_t)blockIdx.x * 256;
+    for (int j = 0; j < 4; j++) slab[(g * 4 + j) * 16 + rc] = acc[j];
+}
+
+// v_mfma_scale_f32_16x16x128_f8f6f4 operand maps, as the tests established
+// them on an MI355X (they differ by format, and from the bf16-style guess):
+//   * lane l works on row (A) or column (B) l&15; g = l>>4.
+//   * fp4: 4 dwords, two elements per byte, the even one in the low nibble;
+//     element e = 0..31 of lane group g is k = 32g + e.
+//   * fp8: 8 dwords, element e in byte e; e = 0..15 is k = 16g + e and
+//     e = 16..31 is k = 64 + 16g + (e-16): a lane holds two 16-wide runs,
+//     64 apart, not one 32-wide block.
+//   * byte 0 of the scale VGPR (op_sel 0) of lane (l&15, g) is the E8M0 scale
+//     of k = 32g .. 32g+31 of that row or column — for fp4 the lane's own
+//     elements, for fp8 elements held by other lanes.
+// With these, D[i][j] = Σ_b 2^(sa[i][b]-127)·2^(sb[b][j]-127)·Σ_{k∈32b..32b+31} a·b
+// for every format pair, mixed ones included.
+template <int FMT>
+__device__ constexpr int mx_k(int g, int e) {
+    return FMT == FMT_E2M1 ? 32 * g + e : 64 * (e >> 4) + 16 * g + (e & 15);
+}
+
+// One lane's 32 element codes, in element order, → its operand registers
+// (fp4 fills the first four dwords; the other four are not read).
+template <int FMT>
+__device__ i32x8 pack_mx(const uint8_t (&code)[32]) {
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 32; e++) {
+        if constexpr (FMT == FMT_E2M1) w[e >> 3] |= (code[e] & 15u) << (4 * (e & 7));
+        else w[e >> 2] |= (uint32_t)code[e] << (8 * (e & 3));
+    }
+    i32x8 v;
+#pragma unroll
+    for (int i = 0; i < 8; i++) v[i] = (int)w[i];
+    return v;
+}
+
+template <int AF, int BF>
+__global__ void mfma_mx_tile(const uint8_t* __restrict__ A,   // 16×128 codes
+                             const uint8_t* __restrict__ B,   // 128×16 codes
+                             const uint8_t* __restrict__ SA,  // 16×4 E8M0
+                             const uint8_t* __restrict__ SB,  // 4×16 E8M0
+                             float* __restrict__ D) {         // gridDim.x × 16×16
+    int l = threadIdx.x & (WAVE - 1);
+    int rc = l & 15, g = l >> 4;
+    uint8_t ca[32], cb[32];
+#pragma unroll
+    for (int e = 0; e < 32; e++) {
+        ca[e] = A[rc * 128 + mx_k<AF>(g, e)];
+        cb[e] = B[mx_k<BF>(g, e) * 16 + rc];
+    }
+    i32x8 a = pack_mx<AF>(ca), b = pack_mx<BF>(cb);
+    int sa = SA[rc * 4 + g], sb = SB[g * 16 + rc];
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, AF, BF, 0, sa, 0, sb);
+    float* slab = D + (size_t)blockIdx.x * 256;
+    for (int j = 0; j < 4; j++) slab[(g * 4 + j) * 16 + rc] = acc[j];
+}
+
+// Throughput burn on the instruction the tile tests verified. Element e of
+// lane l (k = mx_k(l>>4, e) of row or column l&15) is the code of the integer
+// 1 + (l+e)%3 for A and 1 + (l^e)%3 for B, so the operand map matters; both
+// scales are 127 (×1). Accumulator n starts at n, which keeps the eight
+// chains distinct for the compiler, and every partial sum is an exact
+// integer: one MFMA adds at most 128·9 = 1152 to an element, so the per-lane
+// sum, at most 112 + 32·1152·iters, stays below 2^24 for iters ≤ 455 (and a
+// single accumulator up to iters = 14563). Longer burns round, identically in
+// every wave.
+// Eight independent accumulators per wave and two waves per SIMD: the
+// dependent-accumulator latency of this form is not documented, and eight
+// back-to-back issues (8×16 cycles at the FP4 rate) cover any plausible one.
+// Measured on MI355X: ≈4300 TF MX-fp8, ≈8200 TF MX-fp4 (profiles/mfma_lowp.md).
+constexpr int MX_BURN_ACCS = 8;
+
+template <int FMT>
+__global__ void __launch_bounds__(256, 2)
+mfma_mx_burn(float* __restrict__ out, int iters) {
+    int l = threadIdx.x & (WAVE - 1);
+    // codes of 1, 2, 3
+    constexpr uint32_t c1 = FMT == FMT_E2M1 ? 0x2 : 0x38;
+    constexpr uint32_t c2 = FMT == FMT_E2M1 ? 0x4 : 0x40;
+    constexpr uint32_t c3 = FMT == FMT_E2M1 ? 0x5 : 0x44;
+    uint8_t ca[32], cb[32];
+#pragma unroll
+    for (int e = 0; e < 32; e++) {
+        int va = (l + e) % 3, vb = (l ^ e) % 3;
+        ca[e] = (uint8_t)(va == 0 ? c1 : va == 1 ? c2 : c3);
+        cb[e] = (uint8_t)(vb == 0 ? c1 : vb == 1 ? c2 : c3);
+    }
+    i32x8 a = pack_mx<FMT>(ca), b = pack_mx<FMT>(cb);
+    f32x4 acc[MX_BURN_ACCS];
+#pragma unroll
+    for (int n = 0; n < MX_BURN_ACCS; n++) acc[n] = {(float)n, (float)n, (float)n, (float)n};
+    for (int it = 0; it < iters; it++) {
+#pragma unroll
+        for (int n = 0; n < MX_BURN_ACCS; n++)
+            acc[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                a, b, acc[n], FMT, FMT, 0, 127, 0, 127);
+    }
+    float s = 0;
+#pragma unroll
+    for (int n = 0; n < MX_BURN_ACCS; n++) s += acc[n][0] + acc[n][1] + acc[n][2] + acc[n][3];
+    // one store per lane
     out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
@@ -824,6 +976,291 @@ py::dict mfma_probe_bf16(int dev, int burn_iters) {
     return d;
 }
 
+// --- FP8 / MX -----------------------------------------------------------------
+
+// "e4m3" / "e5m2" / "e2m1" → the instruction's format number.
+int parse_fmt(const std::string& s, bool allow_fp4, const char* what) {
+    if (s == "e4m3") return FMT_E4M3;
+    if (s == "e5m2") return FMT_E5M2;
+    if (allow_fp4 && s == "e2m1") return FMT_E2M1;
+    throw std::invalid_argument(what);
+}
+
+// A C-contiguous buffer of exactly `count` unsigned bytes.
+const uint8_t* code_buffer(const py::buffer_info& info, size_t count, const char* what) {
+    require(info.format == py::format_descriptor<uint8_t>::format(), what);
+    return (const uint8_t*)tile_buffer(info, 1, count, what);
+}
+
+using fp8_kernel_t = void (*)(const uint8_t*, const uint8_t*, float*);
+using mx_kernel_t = void (*)(const uint8_t*, const uint8_t*, const uint8_t*,
+                             const uint8_t*, float*);
+
+fp8_kernel_t fp8_kernel(int af, int bf) {
+    if (af == FMT_E4M3) return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E4M3, FMT_E4M3>
+                                              : mfma_fp8_tile<FMT_E4M3, FMT_E5M2>;
+    return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E5M2, FMT_E4M3>
+                          : mfma_fp8_tile<FMT_E5M2, FMT_E5M2>;
+}
+
+// cbsz and blgp are immediates, so each format pair is its own kernel.
+template <int AF>
+mx_kernel_t mx_kernel_b(int bf) {
+    switch (bf) {
+        case FMT_E4M3: return mfma_mx_tile<AF, FMT_E4M3>;
+        case FMT_E5M2: return mfma_mx_tile<AF, FMT_E5M2>;
+        default:       return mfma_mx_tile<AF, FMT_E2M1>;
+    }
+}
+
+mx_kernel_t mx_kernel(int af, int bf) {
+    switch (af) {
+        case FMT_E4M3: return mx_kernel_b<FMT_E4M3>(bf);
+        case FMT_E5M2: return mx_kernel_b<FMT_E5M2>(bf);
+        default:       return mx_kernel_b<FMT_E2M1>(bf);
+    }
+}
+
+// One launch of mfma_fp8_tile on `blocks` blocks → blocks × 256 floats.
+std::vector<float> run_fp8_tile(const uint8_t* A, const uint8_t* B, int af, int bf,
+                                int blocks) {
+    std::vector<float> hD((size_t)blocks * 256);
+    DevBuf dA(512), dB(512), dD(hD.size() * 4);
+    HIP_CHECK(hipMemcpy(dA.p, A, 512, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dB.p, B, 512, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(fp8_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
+                       dA.as<const uint8_t>(), dB.as<const uint8_t>(), dD.as<float>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
+    return hD;
+}
+
+// One launch of mfma_mx_tile on `blocks` blocks → blocks × 256 floats.
+std::vector<float> run_mx_tile(const uint8_t* A, const uint8_t* B, const uint8_t* SA,
+                               const uint8_t* SB, int af, int bf, int blocks) {
+    std::vector<float> hD((size_t)blocks * 256);
+    DevBuf dA(2048), dB(2048), dSA(64), dSB(64), dD(hD.size() * 4);
+    HIP_CHECK(hipMemcpy(dA.p, A, 2048, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dB.p, B, 2048, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dSA.p, SA, 64, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dSB.p, SB, 64, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mx_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
+                       dA.as<const uint8_t>(), dB.as<const uint8_t>(),
+                       dSA.as<const uint8_t>(), dSB.as<const uint8_t>(), dD.as<float>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
+    return hD;
+}
+
+py::bytes mfma_fp8_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
+                            const std::string& a_fmt, const std::string& b_fmt,
+                            int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
+    int af = parse_fmt(a_fmt, false, "a_fmt must be 'e4m3' or 'e5m2'");
+    int bf = parse_fmt(b_fmt, false, "b_fmt must be 'e4m3' or 'e5m2'");
+    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
+    const uint8_t* pa = code_buffer(ia, 512, "A_codes must be 16x32 contiguous uint8");
+    const uint8_t* pb = code_buffer(ib, 512, "B_codes must be 32x16 contiguous uint8");
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_fp8_tile(pa, pb, af, bf, blocks));
+}
+
+py::bytes mfma_mx_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
+                           py::buffer A_scales, py::buffer B_scales,
+                           const std::string& a_fmt, const std::string& b_fmt,
+                           int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
+    int af = parse_fmt(a_fmt, true, "a_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
+    int bf = parse_fmt(b_fmt, true, "b_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
+    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
+    py::buffer_info isa = A_scales.request(), isb = B_scales.request();
+    const uint8_t* pa = code_buffer(ia, 2048, "A_codes must be 16x128 contiguous uint8");
+    const uint8_t* pb = code_buffer(ib, 2048, "B_codes must be 128x16 contiguous uint8");
+    const uint8_t* psa = code_buffer(isa, 64, "A_scales must be 16x4 contiguous uint8");
+    const uint8_t* psb = code_buffer(isb, 64, "B_scales must be 4x16 contiguous uint8");
+    for (int i = 0; i < 2048; i++) {
+        require(af != FMT_E2M1 || pa[i] < 16, "A_codes: an e2m1 code must be below 16");
+        require(bf != FMT_E2M1 || pb[i] < 16, "B_codes: an e2m1 code must be below 16");
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_mx_tile(pa, pb, psa, psb, af, bf, blocks));
+}
+
+void launch_mx_burn(int fmt, int blocks, float* out, int iters) {
+    if (fmt == FMT_E2M1)
+        hipLaunchKernelGGL(mfma_mx_burn<FMT_E2M1>, dim3(blocks), dim3(256), 0, 0, out, iters);
+    else
+        hipLaunchKernelGGL(mfma_mx_burn<FMT_E4M3>, dim3(blocks), dim3(256), 0, 0, out, iters);
+}
+
+int parse_burn_fmt(const std::string& s) {
+    if (s == "e4m3") return FMT_E4M3;
+    if (s == "e2m1") return FMT_E2M1;
+    throw std::invalid_argument("fmt must be 'e4m3' or 'e2m1'");
+}
+
+py::dict mfma_mx_burn_run(int dev, const std::string& fmt, int iters, int blocks) {
+    require(dev >= 0, "dev must be >= 0");
+    int f = parse_burn_fmt(fmt);
+    require(iters > 0, "iters must be > 0");
+    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
+    HIP_CHECK(hipSetDevice(dev));
+    blocks = burn_blocks(dev, blocks, 2);
+    std::vector<float> h((size_t)blocks * 256);
+    DevBuf out(h.size() * 4);
+    launch_mx_burn(f, blocks, out.as<float>(), iters);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
+    py::dict d;
+    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
+    d["mismatches"] = burn_mismatches(h);
+    d["blocks"] = blocks;
+    return d;
+}
+
+// Host decoders for the probe's reference (finite codes only).
+double decode_fp8(uint8_t c, int ebits) {
+    int mbits = 7 - ebits, bias = (1 << (ebits - 1)) - 1;
+    int e = (c >> mbits) & ((1 << ebits) - 1), m = c & ((1 << mbits) - 1);
+    double v = e ? std::ldexp(1.0 + m / (double)(1 << mbits), e - bias)
+                 : std::ldexp(m / (double)(1 << mbits), 1 - bias);
+    return (c & 0x80) ? -v : v;
+}
+
+double decode_e2m1(uint8_t c) {
+    static const double mag[8] = {0, 0.5, 1, 1.5, 2, 3, 4, 6};
+    return (c & 8) ? -mag[c & 7] : mag[c & 7];
+}
+
+double decode_code(uint8_t c, int fmt) {
+    return fmt == FMT_E2M1 ? decode_e2m1(c) : decode_fp8(c, fmt == FMT_E4M3 ? 4 : 5);
+}
+
+uint32_t lcg_bits(uint64_t& s) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(s >> 33);
+}
+
+// Exact-tile operand code: e4m3 with random sign and mantissa and exponent
+// field 6..9 (|v| in [0.5, 7.5], step 2^-4 at the least), or any e2m1 code.
+uint8_t exact_code(uint64_t& rng, int fmt) {
+    uint32_t r = lcg_bits(rng);
+    if (fmt == FMT_E2M1) return (uint8_t)(r & 15);
+    return (uint8_t)((r & 0x87) | (6 + ((r >> 8) & 3)) << 3);
+}
+
+struct LowpTile {
+    bool ok;
+    uint64_t bad_slabs;
+};
+
+// The fixed exact tile of one format on `blocks` blocks: MX (K = 128, random
+// scales 127..128 for e4m3, 125..129 for e2m1) or non-scaled fp8 (K = 32).
+// Every product and partial sum is a multiple of the smallest product step q
+// and Σ|a·b| < 2^24·q — e4m3: q = 2^-8, Σ ≤ 128·(7.5·2)^2 = 2^14.8 = 2^22.8·q;
+// e2m1: q = 2^-6, Σ ≤ 128·(6·4)^2 = 2^16.2 = 2^22.2·q — so the fp64 product
+// cast to f32 is the answer under any summation order: the comparison is
+// bitwise, no tolerance.
+LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
+    const int K = mx ? 128 : 32, NB = K / 32;
+    const int s_lo = fmt == FMT_E2M1 ? 125 : 127, s_n = fmt == FMT_E2M1 ? 5 : 2;
+    std::vector<uint8_t> A(16 * 128, 0), B(128 * 16, 0), SA(64, 127), SB(64, 127);
+    uint64_t rng = seed;
+    for (int i = 0; i < 16 * K; i++) A[i] = exact_code(rng, fmt);
+    for (int i = 0; i < K * 16; i++) B[i] = exact_code(rng, fmt);
+    if (mx) {
+        for (uint8_t& s : SA) s = (uint8_t)(s_lo + lcg_bits(rng) % s_n);
+        for (uint8_t& s : SB) s = (uint8_t)(s_lo + lcg_bits(rng) % s_n);
+    }
+    std::vector<float> ref(256);
+    for (int i = 0; i < 16; i++)
+        for (int j = 0; j < 16; j++) {
+            double sum = 0;
+            for (int b = 0; b < NB; b++) {
+                double part = 0;
+                for (int k = 32 * b; k < 32 * b + 32; k++)
+                    part += decode_code(A[i * K + k], fmt) * decode_code(B[k * 16 + j], fmt);
+                sum += std::ldexp(part, SA[i * 4 + b] - 127 + SB[b * 16 + j] - 127);
+            }
+            ref[i * 16 + j] = (float)sum;
+        }
+    std::vector<float> hD = mx
+        ? run_mx_tile(A.data(), B.data(), SA.data(), SB.data(), fmt, fmt, blocks)
+        : run_fp8_tile(A.data(), B.data(), fmt, fmt, blocks);
+    return {std::memcmp(hD.data(), ref.data(), 256 * 4) == 0, slab_mismatches(hD, 256)};
+}
+
+struct LowpBurn {
+    double tflops;
+    float ms;
+    uint64_t mismatches;
+};
+
+LowpBurn lowp_timed_burn(int dev, int fmt, int iters) {
+    int grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
+    std::vector<float> h((size_t)grid * 256);
+    DevBuf out_buf(h.size() * 4);
+    float* out = out_buf.as<float>();
+    launch_mx_burn(fmt, grid, out, 64);
+    HIP_CHECK(hipDeviceSynchronize());
+    hipEvent_t t0, t1;
+    HIP_CHECK(hipEventCreate(&t0));
+    HIP_CHECK(hipEventCreate(&t1));
+    HIP_CHECK(hipEventRecord(t0));
+    launch_mx_burn(fmt, grid, out, iters);
+    HIP_CHECK(hipEventRecord(t1));
+    HIP_CHECK(hipEventSynchronize(t1));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    HIP_CHECK(hipEventDestroy(t0));
+    HIP_CHECK(hipEventDestroy(t1));
+    HIP_CHECK(hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost));
+    // FLOPs: blocks × 4 waves/WG × accumulators × iters × 2·16·16·128
+    double flops = (double)grid * 4.0 * MX_BURN_ACCS * iters * 2.0 * 16 * 16 * 128;
+    return {flops / (ms * 1e9), ms, burn_mismatches(h)};
+}
+
+// FP8 / MX-FP8 / MX-FP4 matrix-core probe: one fixed exact tile per form on
+// 2 blocks per CU (slab 0 bitwise against the host's fp64 product, every
+// other slab bitwise against slab 0), then a timed MX-fp8 and MX-fp4 burn,
+// each after a warm-up launch, whose waves must all agree bit for bit.
+// If a burn rate falls short of the guide's peak (~5 PF MX-fp8, ~10 PF
+// MX-fp4), the things to revisit are the accumulator count (MX_BURN_ACCS = 8),
+// the waves per SIMD (2: two 256-thread workgroups per CU) and the shape
+// (16x16x128; the 32x32x64 form moves half the operand bytes per FLOP).
+// FP6 operands are not probed: same datapath and rate as FP4.
+py::dict mfma_probe_lowp(int dev, int burn_iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(burn_iters > 0, "burn_iters must be > 0");
+    HIP_CHECK(hipSetDevice(dev));
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    LowpTile fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, 0xA4093822299F31D0ull);
+    LowpTile mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, 0x082EFA98EC4E6C89ull);
+    LowpTile mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, 0x452821E638D01377ull);
+    LowpBurn b8 = lowp_timed_burn(dev, FMT_E4M3, burn_iters);
+    LowpBurn b4 = lowp_timed_burn(dev, FMT_E2M1, burn_iters);
+    py::dict d;
+    d["fp8_ok"] = fp8.ok;
+    d["mx_fp8_ok"] = mx8.ok;
+    d["mx_fp4_ok"] = mx4.ok;
+    d["fp8_slab_mismatches"] = fp8.bad_slabs;
+    d["mx_fp8_slab_mismatches"] = mx8.bad_slabs;
+    d["mx_fp4_slab_mismatches"] = mx4.bad_slabs;
+    d["mx_fp8_tflops"] = b8.tflops;
+    d["mx_fp4_tflops"] = b4.tflops;
+    d["mx_fp8_burn_mismatches"] = b8.mismatches;
+    d["mx_fp4_burn_mismatches"] = b4.mismatches;
+    d["mx_fp8_burn_ms"] = b8.ms;
+    d["mx_fp4_burn_ms"] = b4.ms;
+    d["blocks"] = blocks;
+    return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_gpuprobe, m) {
@@ -853,5 +1290,14 @@ PYBIND11_MODULE(_gpuprobe, m) {
           py::arg("bytes") = (size_t)1 << 30, py::arg("steps") = 2000000);
     m.def("mfma_probe_f32", &mfma_probe_f32, py::arg("dev") = 0);
     m.def("mfma_probe_bf16", &mfma_probe_bf16, py::arg("dev") = 0,
+          py::arg("burn_iters") = 20000);
+    m.def("mfma_fp8_tile_run", &mfma_fp8_tile_run, py::arg("dev"), py::arg("A_codes"),
+          py::arg("B_codes"), py::arg("a_fmt"), py::arg("b_fmt"), py::arg("blocks") = 1);
+    m.def("mfma_mx_tile_run", &mfma_mx_tile_run, py::arg("dev"), py::arg("A_codes"),
+          py::arg("B_codes"), py::arg("A_scales"), py::arg("B_scales"),
+          py::arg("a_fmt"), py::arg("b_fmt"), py::arg("blocks") = 1);
+    m.def("mfma_mx_burn_run", &mfma_mx_burn_run, py::arg("dev"), py::arg("fmt"),
+          py::arg("iters") = 64, py::arg("blocks") = 0);
+    m.def("mfma_probe_lowp", &mfma_probe_lowp, py::arg("dev") = 0,
           py::arg("burn_iters") = 20000);
 }
