@@ -82,6 +82,15 @@ class ProbeReport:
     mfma_mx_fp4_slab_mismatches: int = -1
     mx_fp8_burn_mismatches: int = -1
     mx_fp4_burn_mismatches: int = -1
+    # placement-recording unit sweep (probe_device(unit_sweep=True))
+    unit_sweep_ran: bool = False
+    sweep_cus_seen: int = -1
+    sweep_simds_seen: int = -1
+    sweep_simds_missing: int = -1
+    sweep_launches: int = 0
+    sweep_ms: float = 0.0
+    sweep_exclusive: bool = False
+    faulty_units: List[Dict] = field(default_factory=list)
     passed: bool = False
     failures: List[str] = field(default_factory=list)
 
@@ -99,12 +108,17 @@ def probe_device(
     low_precision: bool = False,
     fp8_tflops_floor: Optional[float] = None,
     fp4_tflops_floor: Optional[float] = None,
+    unit_sweep: bool = False,
 ) -> ProbeReport:
     """Run the full probe suite on one GPU; raises only on infrastructure
     errors — a sick GPU yields passed=False with reasons.
 
     `low_precision=True` adds the FP8 and block-scaled MX (FP8/FP4)
-    matrix-core probes; they exist on gfx950 only."""
+    matrix-core probes; they exist on gfx950 only.
+
+    `unit_sweep=True` adds the placement-recording sweep: the exact tiles
+    through every SIMD of every CU, failures named by XCD / SE / CU / SIMD,
+    and incomplete coverage reported as a failure."""
     g = _ext()
     rep = ProbeReport(device=dev)
     info = g.device_info(dev)
@@ -197,6 +211,9 @@ def probe_device(
         _probe_low_precision(g, rep, dev, burn_iters, is_mi355x,
                              fp8_tflops_floor, fp4_tflops_floor)
 
+    if unit_sweep:
+        _probe_unit_sweep(g, rep, dev, low_precision and is_mi355x)
+
     mt = g.memtest(dev, memtest_bytes)
     rep.memtest_mismatches = int(mt["mismatches"])
     if rep.memtest_mismatches:
@@ -250,6 +267,59 @@ def _probe_low_precision(g, rep: ProbeReport, dev: int, burn_iters: int,
         if tflops < floor:
             rep.failures.append(
                 f"{label} MFMA {tflops:.0f} TFLOP/s < floor {floor:.0f}")
+
+
+def _probe_unit_sweep(g, rep: ProbeReport, dev: int, low_precision: bool) -> None:
+    """The unit sweep: one failure line per faulty unit and kind, one for
+    incomplete coverage, one for a suspect id layout, one per kind whose
+    golden tile could not be trusted."""
+    from . import placement
+
+    sw = g.unit_sweep_probe(dev, low_precision)
+    summary = placement.summarise(sw["records"], rep.compute_units,
+                                  int(sw["waves_per_block"]))
+    rep.unit_sweep_ran = True
+    rep.sweep_cus_seen = int(summary["cus_seen"])
+    rep.sweep_simds_seen = int(summary["simds_seen"])
+    rep.sweep_simds_missing = int(summary["missing"])
+    rep.sweep_launches = int(sw["launches"])
+    rep.sweep_ms = float(sw["sweep_ms"])
+    rep.sweep_exclusive = bool(sw["exclusive"])
+    reps = int(sw["reps"])
+    for kind, ok in sw["golden_ok"].items():
+        if not ok:
+            rep.failures.append(
+                f"unit sweep: no trusted golden {placement.KIND_LABEL[kind]}, "
+                "kind not swept")
+    for f in summary["faulty_units"]:
+        unit, kind = f["unit"], f["kind"]
+        name = placement.format_unit(unit)
+        rep.faulty_units.append({
+            "unit": name, "kind": kind, "xcd": unit.xcd, "se": unit.se,
+            "sh": unit.sh, "cu": unit.cu, "simd": unit.simd,
+            "mismatches": f["mismatches"], "waves": f["waves"],
+            "hw_id": f["hw_id"], "xcc_id": f["xcc_id"],
+        })
+        if kind == "lds":
+            detail = f"{f['mismatches']} wrong words in {f['waves']} waves' read-back"
+        else:
+            detail = (f"{f['mismatches']} wrong elements in {f['waves']} waves "
+                      f"x {reps} repetitions")
+        rep.failures.append(
+            f"unit sweep: {placement.KIND_LABEL[kind]} wrong on {name} ({detail})")
+    if rep.sweep_simds_missing:
+        line = (f"unit sweep: {rep.sweep_simds_missing} of "
+                f"{summary['simds_expected']} SIMDs never ran it")
+        if summary["partial_cus"]:
+            line += " (CUs seen in part: " + ", ".join(
+                f"{c['unit']} SIMDs {c['simds_seen']}"
+                for c in summary["partial_cus"][:8]) + ")"
+        rep.failures.append(line)
+    if summary["layout_suspect"]:
+        rep.failures.append(
+            f"unit sweep: hardware ids do not fit the assumed layout "
+            f"({rep.sweep_cus_seen} CU keys on {rep.compute_units} CUs, or one "
+            "workgroup on two CUs); unit names are not to be trusted")
 
 
 def _probe_as_dict(dev: int, kw: Dict) -> Dict:

@@ -37,6 +37,10 @@
 //     returns mismatch count (catches dead HBM channels). corrupt_offsets
 //     flips words of the live buffer between write and check, to show the
 //     probe can fail.
+//   * unit_sweep      : one LDS-exclusive workgroup per CU puts the exact tiles
+//     above through every SIMD, checks the CU's whole LDS allocation, and
+//     records the hardware ids (XCD / SE / CU / SIMD) each wave ran on, so
+//     coverage is shown and a failure has an address. poison is its test hook.
 //   * *_run / hbm_copy_check : raw entry points that return what a kernel
 //     computed, for tests against independent references.
 //
@@ -396,6 +400,235 @@ mfma_mx_burn(float* __restrict__ out, int iters) {
     for (int n = 0; n < MX_BURN_ACCS; n++) s += acc[n][0] + acc[n][1] + acc[n][2] + acc[n][3];
     // one store per lane
     out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+// ---------------------------------------------------------------------------
+// Unit sweep: the probes' exact tiles through every SIMD of every CU, with a
+// record of where each wave ran.
+//
+// One workgroup asks for more than half of a CU's 160 KiB of LDS, so two can
+// never share a CU; a grid of one workgroup per CU whose workgroups outlive
+// the dispatcher's start spread (0.34–0.69 µs for 1024 blocks) therefore has
+// one on every CU at once. Nothing else is assumed about placement: each wave
+// reads HW_REG_HW_ID (wave slot, SIMD, CU, SH, SE) and HW_REG_XCC_ID (XCD)
+// and the host decides from the records which units were covered. A workgroup
+// never waits for another one.
+//
+// Every wave recomputes each selected tile `reps` times from a zero
+// accumulator and compares its registers bit for bit with the golden tile the
+// host supplies (same inputs and lane maps as the tile kernels above). The
+// inputs are loop-invariant and the MFMA builtins are pure, so one operand
+// goes through an empty volatile asm in each repetition: without it the
+// compiler computes the tile once, outside the loop.
+//
+// LDS: the workgroup fills its whole allocation with an address pattern and
+// reads it back mirrored (word i was written by thread i % n and is read by
+// thread n-1 - i % n, which sits in another wave), counting wrong words.
+//
+// Poison is the test hook that shows the sweep can fail: a wave whose own
+// hardware ids match XORs poison_xor into element 0 of lane 0 of that kind's
+// result in every repetition, or (kind = lds) into one word of the
+// workgroup's own allocation between fill and read-back.
+//
+// Record per wave, eight uint32: hw_id, xcc_id, then the wrong-element counts
+// of f32, bf16, fp8, mx_fp8, mx_fp4 and the wave's share of wrong LDS words.
+// ---------------------------------------------------------------------------
+enum SweepKind { SK_F32 = 0, SK_BF16, SK_FP8, SK_MX_FP8, SK_MX_FP4, SK_LDS, SK_COUNT };
+
+constexpr int SWEEP_RECORD_WORDS = 8;
+constexpr size_t CU_LDS_BYTES = 160 << 10;
+
+struct SweepInputs {
+    float a32[64], b32[64], g32[256];
+    uint16_t a16[512], b16[512];
+    float g16[1024];
+    uint8_t a8[512], b8[512];
+    float g8[256];
+    uint8_t amx8[2048], bmx8[2048], samx8[64], sbmx8[64];
+    float gmx8[256];
+    uint8_t amx4[2048], bmx4[2048], samx4[64], sbmx4[64];
+    float gmx4[256];
+};
+
+struct SweepParams {
+    uint32_t kinds;      // bit k set = SweepKind k selected
+    int reps;
+    uint32_t lds_words;  // the dynamic LDS allocation; a multiple of blockDim.x
+    int poison_kind;     // a SweepKind, or -1
+    uint32_t poison_xcc, poison_cu_key, poison_simd, poison_xor;
+};
+
+// s_getreg_b32 immediate: register id, bit offset 0, all 32 bits.
+constexpr int sweep_hwreg(int id) { return id | (31 << 11); }
+constexpr int HWREG_HW_ID = 4, HWREG_XCC_ID = 20;
+
+// Makes `v` opaque to the compiler at this point of every repetition.
+template <class V>
+__device__ __forceinline__ void sweep_relive(V& v) {
+    static_assert(sizeof(V) % 4 == 0, "whole registers");
+    uint32_t w[sizeof(V) / 4];
+    __builtin_memcpy(w, &v, sizeof(V));
+    asm volatile("" : "+v"(w[0]));
+    __builtin_memcpy(&v, w, sizeof(V));
+}
+
+template <int N, class Acc>
+__device__ __forceinline__ uint32_t sweep_count_bad(const Acc& acc, const float (&gold)[N],
+                                                    uint32_t flip) {
+    uint32_t bad = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        uint32_t got = __float_as_uint(acc[j]);
+        if (j == 0) got ^= flip;
+        bad += got != __float_as_uint(gold[j]);
+    }
+    return bad;
+}
+
+__device__ __forceinline__ uint32_t sweep_wave_sum(uint32_t v) {
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+template <int FMT>
+__device__ uint32_t sweep_mx(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B,
+                             const uint8_t* __restrict__ SA, const uint8_t* __restrict__ SB,
+                             const float* __restrict__ G, int l, int reps, uint32_t flip) {
+    int rc = l & 15, g = l >> 4;
+    uint8_t ca[32], cb[32];
+#pragma unroll
+    for (int e = 0; e < 32; e++) {
+        ca[e] = A[rc * 128 + mx_k<FMT>(g, e)];
+        cb[e] = B[mx_k<FMT>(g, e) * 16 + rc];
+    }
+    i32x8 a = pack_mx<FMT>(ca), b = pack_mx<FMT>(cb);
+    int sa = SA[rc * 4 + g], sb = SB[g * 16 + rc];
+    float gold[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) gold[j] = G[(g * 4 + j) * 16 + rc];
+    uint32_t n = 0;
+    for (int r = 0; r < reps; r++) {
+        sweep_relive(a);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, FMT, FMT, 0, sa, 0, sb);
+        n += sweep_count_bad<4>(acc, gold, flip);
+    }
+    return n;
+}
+
+__global__ void __launch_bounds__(1024)
+unit_sweep(const SweepInputs* __restrict__ in, SweepParams p, uint32_t* __restrict__ records) {
+    extern __shared__ uint32_t sweep_lds[];
+    const int l = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const uint32_t hw_id = __builtin_amdgcn_s_getreg(sweep_hwreg(HWREG_HW_ID));
+    const uint32_t xcc_id = __builtin_amdgcn_s_getreg(sweep_hwreg(HWREG_XCC_ID));
+    const bool on_cu = p.poison_kind >= 0 && (xcc_id & 15u) == p.poison_xcc &&
+                       ((hw_id >> 8) & 255u) == p.poison_cu_key;
+    const bool on_simd = on_cu && ((hw_id >> 4) & 3u) == p.poison_simd;
+    auto flip_for = [&](int kind) -> uint32_t {
+        return on_simd && p.poison_kind == kind && l == 0 ? p.poison_xor : 0u;
+    };
+    uint32_t bad[SK_COUNT] = {0, 0, 0, 0, 0, 0};
+
+    if (p.kinds & (1u << SK_LDS)) {
+        const uint32_t n = blockDim.x, words = p.lds_words;
+        for (uint32_t i = threadIdx.x; i < words; i += n)
+            sweep_lds[i] = i * 0x9E3779B9u ^ 0xA5A55A5Au;
+        __syncthreads();
+        // words >= n >= 64, so the flipped word lies inside the allocation
+        if (on_cu && p.poison_kind == SK_LDS && threadIdx.x == 0)
+            sweep_lds[words / 2 + 1] ^= p.poison_xor;
+        __syncthreads();
+        uint32_t wrong = 0;
+        for (uint32_t i = threadIdx.x; i < words; i += n) {
+            uint32_t j = words - 1 - i;
+            wrong += sweep_lds[j] != (j * 0x9E3779B9u ^ 0xA5A55A5Au);
+        }
+        bad[SK_LDS] = sweep_wave_sum(wrong);
+    }
+
+    if (p.kinds & (1u << SK_F32)) {
+        int rc = l & 15, k = l >> 4;
+        float a = in->a32[rc * 4 + k], b = in->b32[k * 16 + rc];
+        float gold[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) gold[j] = in->g32[(k * 4 + j) * 16 + rc];
+        uint32_t flip = flip_for(SK_F32), n = 0;
+        for (int r = 0; r < p.reps; r++) {
+            sweep_relive(a);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+            n += sweep_count_bad<4>(acc, gold, flip);
+        }
+        bad[SK_F32] = sweep_wave_sum(n);
+    }
+
+    if (p.kinds & (1u << SK_BF16)) {
+        int half = l >> 5, lane32 = l & 31;
+        const __bf16* A = reinterpret_cast<const __bf16*>(in->a16);
+        const __bf16* B = reinterpret_cast<const __bf16*>(in->b16);
+        bf16x8 a, b;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            a[j] = A[lane32 * 16 + half * 8 + j];
+            b[j] = B[(half * 8 + j) * 32 + lane32];
+        }
+        float gold[16];
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++)
+            gold[reg] = in->g16[((reg & 3) + 8 * (reg >> 2) + 4 * half) * 32 + lane32];
+        uint32_t flip = flip_for(SK_BF16), n = 0;
+        for (int r = 0; r < p.reps; r++) {
+            sweep_relive(a);
+            f32x16 acc = {};
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+            n += sweep_count_bad<16>(acc, gold, flip);
+        }
+        bad[SK_BF16] = sweep_wave_sum(n);
+    }
+
+    if (p.kinds & (1u << SK_FP8)) {
+        int rc = l & 15, g = l >> 4;
+        uint64_t a = 0, b = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            a |= (uint64_t)in->a8[rc * 32 + 8 * g + j] << (8 * j);
+            b |= (uint64_t)in->b8[(8 * g + j) * 16 + rc] << (8 * j);
+        }
+        float gold[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) gold[j] = in->g8[(g * 4 + j) * 16 + rc];
+        uint32_t flip = flip_for(SK_FP8), n = 0;
+        for (int r = 0; r < p.reps; r++) {
+            sweep_relive(a);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
+            n += sweep_count_bad<4>(acc, gold, flip);
+        }
+        bad[SK_FP8] = sweep_wave_sum(n);
+    }
+
+    if (p.kinds & (1u << SK_MX_FP8))
+        bad[SK_MX_FP8] = sweep_wave_sum(sweep_mx<FMT_E4M3>(
+            in->amx8, in->bmx8, in->samx8, in->sbmx8, in->gmx8, l, p.reps,
+            flip_for(SK_MX_FP8)));
+    if (p.kinds & (1u << SK_MX_FP4))
+        bad[SK_MX_FP4] = sweep_wave_sum(sweep_mx<FMT_E2M1>(
+            in->amx4, in->bmx4, in->samx4, in->sbmx4, in->gmx4, l, p.reps,
+            flip_for(SK_MX_FP4)));
+
+    if (l == 0) {
+        uint32_t* rec = records +
+            ((size_t)blockIdx.x * (blockDim.x / WAVE) + wave) * SWEEP_RECORD_WORDS;
+        rec[0] = hw_id;
+        rec[1] = xcc_id;
+        rec[2] = bad[SK_F32];
+        rec[3] = bad[SK_BF16];
+        rec[4] = bad[SK_FP8];
+        rec[5] = bad[SK_MX_FP8];
+        rec[6] = bad[SK_MX_FP4];
+        rec[7] = bad[SK_LDS];
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -805,10 +1038,12 @@ py::bytes mfma_f32_tile_run(int dev, py::buffer A, py::buffer B, py::object C,
     return as_bytes(run_f32_tile(pa, pb, pc, blocks));
 }
 
-py::dict mfma_probe_f32(int dev) {
-    require(dev >= 0, "dev must be >= 0");
-    HIP_CHECK(hipSetDevice(dev));
-    std::vector<float> hA(16 * 4), hB(4 * 16), ref(16 * 16, 0.f);
+// The f32 probe's fixed tile: A (16×4), B (4×16) and the host's product.
+void f32_probe_tile(std::vector<float>& hA, std::vector<float>& hB,
+                    std::vector<float>& ref) {
+    hA.assign(16 * 4, 0.f);
+    hB.assign(4 * 16, 0.f);
+    ref.assign(16 * 16, 0.f);
     // Full-mantissa inputs over 8 binades: products and partial sums round at
     // every step, so only the documented k-ordered fmaf chain reproduces the
     // bits (dyadic inputs would pass under any order or internal width).
@@ -819,6 +1054,13 @@ py::dict mfma_probe_f32(int dev) {
         for (int j = 0; j < 16; j++)
             for (int k = 0; k < 4; k++)
                 ref[i * 16 + j] = fmaf(hA[i * 4 + k], hB[k * 16 + j], ref[i * 16 + j]);
+}
+
+py::dict mfma_probe_f32(int dev) {
+    require(dev >= 0, "dev must be >= 0");
+    HIP_CHECK(hipSetDevice(dev));
+    std::vector<float> hA, hB, ref;
+    f32_probe_tile(hA, hB, ref);
     // 2 blocks per CU: every CU's matrix cores run the tile
     int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
     std::vector<float> hD = run_f32_tile(hA.data(), hB.data(), nullptr, blocks);
@@ -908,24 +1150,25 @@ py::dict mfma_bf16_burn_run(int dev, int iters, int blocks) {
     return d;
 }
 
-py::dict mfma_probe_bf16(int dev, int burn_iters) {
-    require(dev >= 0, "dev must be >= 0");
-    require(burn_iters > 0, "burn_iters must be > 0");
-    HIP_CHECK(hipSetDevice(dev));
-    // --- correctness tile ---
-    // Random bf16 values over 8 binades (all 8 significand bits in play).
-    // Each bf16×bf16 product is exact in f32 and the 16 additions lose at
-    // most one ulp each in any order, so |D − ref| ≤ 16·2^-23·Σ|a·b| holds
-    // for a healthy matrix core whatever its internal summation order; a
-    // mapping error is O(1) relative.
+// The bf16 probe's fixed tile inputs, as bf16 bit patterns: A (32×16) and
+// B (16×32), random values over 8 binades (all 8 significand bits in play).
+void bf16_probe_inputs(std::vector<uint16_t>& hA, std::vector<uint16_t>& hB) {
     uint64_t rng = 0x13198A2E03707344ull;
-    std::vector<uint16_t> hA(32 * 16), hB(16 * 32);
+    hA.assign(32 * 16, 0);
+    hB.assign(16 * 32, 0);
     for (uint16_t& v : hA) v = bf16_round_bits(lcg_f32(rng));
     for (uint16_t& v : hB) v = bf16_round_bits(lcg_f32(rng));
-    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    std::vector<float> hD = run_bf16_tile(hA.data(), hB.data(), blocks);
-    double max_rel_err = 0;
+}
+
+// Each bf16×bf16 product is exact in f32 and the 16 additions lose at most
+// one ulp each in any order, so |D − ref| ≤ 16·2^-23·Σ|a·b| holds for a
+// healthy matrix core whatever its internal summation order; a mapping error
+// is O(1) relative. `D` is one 32×32 slab.
+bool bf16_tile_within_bound(const std::vector<uint16_t>& hA,
+                            const std::vector<uint16_t>& hB, const float* D,
+                            double& max_rel_err) {
     bool tile_ok = true;
+    max_rel_err = 0;
     for (int i = 0; i < 32; i++)
         for (int j = 0; j < 32; j++) {
             double ref = 0, mag = 0;
@@ -935,13 +1178,27 @@ py::dict mfma_probe_bf16(int dev, int burn_iters) {
                 ref += p;
                 mag += std::fabs(p);
             }
-            double err = std::fabs((double)hD[i * 32 + j] - ref);
+            double err = std::fabs((double)D[i * 32 + j] - ref);
             if (!(err <= 16.0 * 0x1p-23 * mag)) tile_ok = false;   // NaN fails
             if (!std::isnan(max_rel_err)) {
                 double rel = err / std::max(1.0, std::fabs(ref));
                 max_rel_err = std::isnan(rel) ? rel : std::max(max_rel_err, rel);
             }
         }
+    return tile_ok;
+}
+
+py::dict mfma_probe_bf16(int dev, int burn_iters) {
+    require(dev >= 0, "dev must be >= 0");
+    require(burn_iters > 0, "burn_iters must be > 0");
+    HIP_CHECK(hipSetDevice(dev));
+    // --- correctness tile ---
+    std::vector<uint16_t> hA, hB;
+    bf16_probe_inputs(hA, hB);
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    std::vector<float> hD = run_bf16_tile(hA.data(), hB.data(), blocks);
+    double max_rel_err = 0;
+    bool tile_ok = bf16_tile_within_bound(hA, hB, hD.data(), max_rel_err);
     uint64_t bad_slabs = slab_mismatches(hD, 1024);
 
     // --- throughput burn ---
@@ -1159,17 +1416,31 @@ struct LowpTile {
     uint64_t bad_slabs;
 };
 
-// The fixed exact tile of one format on `blocks` blocks: MX (K = 128, random
-// scales 127..128 for e4m3, 125..129 for e2m1) or non-scaled fp8 (K = 32).
+struct LowpOperands {
+    std::vector<uint8_t> A, B, SA, SB;   // codes (16×K, K×16) and E8M0 scales
+    std::vector<float> ref;              // the host's 16×16 product
+};
+
+constexpr uint64_t LOWP_SEED_FP8 = 0xA4093822299F31D0ull;
+constexpr uint64_t LOWP_SEED_MX_FP8 = 0x082EFA98EC4E6C89ull;
+constexpr uint64_t LOWP_SEED_MX_FP4 = 0x452821E638D01377ull;
+
+// The fixed exact tile of one format: MX (K = 128, random scales 127..128 for
+// e4m3, 125..129 for e2m1) or non-scaled fp8 (K = 32).
 // Every product and partial sum is a multiple of the smallest product step q
 // and Σ|a·b| < 2^24·q — e4m3: q = 2^-8, Σ ≤ 128·(7.5·2)^2 = 2^14.8 = 2^22.8·q;
 // e2m1: q = 2^-6, Σ ≤ 128·(6·4)^2 = 2^16.2 = 2^22.2·q — so the fp64 product
 // cast to f32 is the answer under any summation order: the comparison is
 // bitwise, no tolerance.
-LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
+LowpOperands lowp_exact_operands(int fmt, bool mx, uint64_t seed) {
     const int K = mx ? 128 : 32, NB = K / 32;
     const int s_lo = fmt == FMT_E2M1 ? 125 : 127, s_n = fmt == FMT_E2M1 ? 5 : 2;
-    std::vector<uint8_t> A(16 * 128, 0), B(128 * 16, 0), SA(64, 127), SB(64, 127);
+    LowpOperands op;
+    op.A.assign(16 * 128, 0);
+    op.B.assign(128 * 16, 0);
+    op.SA.assign(64, 127);
+    op.SB.assign(64, 127);
+    std::vector<uint8_t>&A = op.A, &B = op.B, &SA = op.SA, &SB = op.SB;
     uint64_t rng = seed;
     for (int i = 0; i < 16 * K; i++) A[i] = exact_code(rng, fmt);
     for (int i = 0; i < K * 16; i++) B[i] = exact_code(rng, fmt);
@@ -1177,7 +1448,7 @@ LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
         for (uint8_t& s : SA) s = (uint8_t)(s_lo + lcg_bits(rng) % s_n);
         for (uint8_t& s : SB) s = (uint8_t)(s_lo + lcg_bits(rng) % s_n);
     }
-    std::vector<float> ref(256);
+    op.ref.assign(256, 0.f);
     for (int i = 0; i < 16; i++)
         for (int j = 0; j < 16; j++) {
             double sum = 0;
@@ -1187,12 +1458,19 @@ LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
                     part += decode_code(A[i * K + k], fmt) * decode_code(B[k * 16 + j], fmt);
                 sum += std::ldexp(part, SA[i * 4 + b] - 127 + SB[b * 16 + j] - 127);
             }
-            ref[i * 16 + j] = (float)sum;
+            op.ref[i * 16 + j] = (float)sum;
         }
+    return op;
+}
+
+// The exact tile above on `blocks` blocks: slab 0 against the host, every
+// other slab against slab 0.
+LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
+    LowpOperands op = lowp_exact_operands(fmt, mx, seed);
     std::vector<float> hD = mx
-        ? run_mx_tile(A.data(), B.data(), SA.data(), SB.data(), fmt, fmt, blocks)
-        : run_fp8_tile(A.data(), B.data(), fmt, fmt, blocks);
-    return {std::memcmp(hD.data(), ref.data(), 256 * 4) == 0, slab_mismatches(hD, 256)};
+        ? run_mx_tile(op.A.data(), op.B.data(), op.SA.data(), op.SB.data(), fmt, fmt, blocks)
+        : run_fp8_tile(op.A.data(), op.B.data(), fmt, fmt, blocks);
+    return {std::memcmp(hD.data(), op.ref.data(), 256 * 4) == 0, slab_mismatches(hD, 256)};
 }
 
 struct LowpBurn {
@@ -1239,9 +1517,9 @@ py::dict mfma_probe_lowp(int dev, int burn_iters) {
     require(burn_iters > 0, "burn_iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    LowpTile fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, 0xA4093822299F31D0ull);
-    LowpTile mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, 0x082EFA98EC4E6C89ull);
-    LowpTile mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, 0x452821E638D01377ull);
+    LowpTile fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, LOWP_SEED_FP8);
+    LowpTile mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, LOWP_SEED_MX_FP8);
+    LowpTile mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, LOWP_SEED_MX_FP4);
     LowpBurn b8 = lowp_timed_burn(dev, FMT_E4M3, burn_iters);
     LowpBurn b4 = lowp_timed_burn(dev, FMT_E2M1, burn_iters);
     py::dict d;
@@ -1258,6 +1536,301 @@ py::dict mfma_probe_lowp(int dev, int burn_iters) {
     d["mx_fp8_burn_ms"] = b8.ms;
     d["mx_fp4_burn_ms"] = b4.ms;
     d["blocks"] = blocks;
+    return d;
+}
+
+// --- unit sweep -----------------------------------------------------------------
+
+const char* const SWEEP_KIND_NAMES[SK_COUNT] = {"f32", "bf16", "fp8", "mx_fp8", "mx_fp4", "lds"};
+
+constexpr int SWEEP_MAX_REPS = 1 << 20;
+constexpr int SWEEP_MAX_BLOCKS = 4096;
+// Measured on MI355X (profiles/unit_sweep.md): the four waves of a 256-thread
+// workgroup sit on four SIMDs, and with the LDS check in the launch one
+// repetition already covered all 1024 SIMDs in a first launch, three runs of
+// three; the default is that smallest count doubled once.
+constexpr int SWEEP_THREADS = 256;
+constexpr int SWEEP_DEFAULT_REPS = 2;
+constexpr int SWEEP_MAX_LAUNCHES = 3;
+constexpr size_t SWEEP_LDS_GRANULE = 4096;   // a multiple of 4 × the largest block
+
+int sweep_kind(const std::string& s, const char* what) {
+    for (int k = 0; k < SK_COUNT; k++)
+        if (s == SWEEP_KIND_NAMES[k]) return k;
+    throw std::invalid_argument(what);
+}
+
+uint32_t sweep_kind_mask(const std::vector<std::string>& kinds) {
+    require(!kinds.empty(), "kinds must not be empty");
+    uint32_t mask = 0;
+    for (const std::string& s : kinds)
+        mask |= 1u << sweep_kind(
+            s, "kinds must be among 'f32', 'bf16', 'fp8', 'mx_fp8', 'mx_fp4', 'lds'");
+    return mask;
+}
+
+// poison = (xcc_id, cu_key, simd_id, kind, xor_bits) or None → SweepParams.
+void sweep_parse_poison(const py::object& poison, uint32_t kinds, SweepParams& p) {
+    p.poison_kind = -1;
+    p.poison_xcc = p.poison_cu_key = p.poison_simd = p.poison_xor = 0;
+    if (poison.is_none()) return;
+    long long xcc, cu, simd, bits;
+    std::string kind;
+    require(py::isinstance<py::tuple>(poison) || py::isinstance<py::list>(poison),
+            "poison must be (xcc_id, cu_key, simd_id, kind, xor_bits)");
+    try {
+        py::tuple t = py::cast<py::tuple>(poison);
+        require(t.size() == 5, "poison must be (xcc_id, cu_key, simd_id, kind, xor_bits)");
+        xcc = py::cast<long long>(t[0]);
+        cu = py::cast<long long>(t[1]);
+        simd = py::cast<long long>(t[2]);
+        kind = py::cast<std::string>(t[3]);
+        bits = py::cast<long long>(t[4]);
+    } catch (const py::cast_error&) {
+        throw std::invalid_argument("poison must be (xcc_id, cu_key, simd_id, kind, xor_bits)");
+    }
+    require(xcc >= 0 && xcc <= 15, "poison xcc_id must be in 0..15");
+    require(cu >= 0 && cu <= 255, "poison cu_key must be in 0..255");
+    require(simd >= 0 && simd <= 3, "poison simd_id must be in 0..3");
+    p.poison_kind = sweep_kind(kind, "poison kind must be one of the six kind names");
+    require(kinds >> p.poison_kind & 1, "poison kind must be among the selected kinds");
+    require(bits >= 1 && bits <= 0xffffffffll, "poison xor_bits must be in 1..2^32-1");
+    p.poison_xcc = (uint32_t)xcc;
+    p.poison_cu_key = (uint32_t)cu;
+    p.poison_simd = (uint32_t)simd;
+    p.poison_xor = (uint32_t)bits;
+}
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIP_CHECK(hipEventCreate(&e)); }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+};
+
+// Inputs and golden tiles of the selected kinds. f32, fp8, MX-fp8 and MX-fp4
+// are the host references of mfma_probe_f32 and mfma_probe_lowp; bf16 has no
+// bitwise host reference, so its golden tile is a one-block mfma_bf16_tile
+// launch that passed the probe's tolerance check (else golden_ok[bf16] = false
+// and the kind is dropped from the sweep).
+struct SweepSetup {
+    SweepInputs in;
+    uint32_t kinds;                 // what will run
+    bool golden_ok[SK_COUNT];
+};
+
+void sweep_prepare(uint32_t kinds, SweepSetup& s) {
+    std::memset(&s.in, 0, sizeof(s.in));
+    s.kinds = kinds;
+    for (bool& ok : s.golden_ok) ok = true;
+    if (kinds & (1u << SK_F32)) {
+        std::vector<float> a, b, ref;
+        f32_probe_tile(a, b, ref);
+        std::memcpy(s.in.a32, a.data(), sizeof(s.in.a32));
+        std::memcpy(s.in.b32, b.data(), sizeof(s.in.b32));
+        std::memcpy(s.in.g32, ref.data(), sizeof(s.in.g32));
+    }
+    if (kinds & (1u << SK_BF16)) {
+        std::vector<uint16_t> a, b;
+        bf16_probe_inputs(a, b);
+        std::vector<float> d = run_bf16_tile(a.data(), b.data(), 1);
+        double max_rel_err = 0;
+        if (bf16_tile_within_bound(a, b, d.data(), max_rel_err)) {
+            std::memcpy(s.in.a16, a.data(), sizeof(s.in.a16));
+            std::memcpy(s.in.b16, b.data(), sizeof(s.in.b16));
+            std::memcpy(s.in.g16, d.data(), sizeof(s.in.g16));
+        } else {
+            s.golden_ok[SK_BF16] = false;
+            s.kinds &= ~(1u << SK_BF16);
+        }
+    }
+    if (kinds & (1u << SK_FP8)) {
+        LowpOperands op = lowp_exact_operands(FMT_E4M3, false, LOWP_SEED_FP8);
+        std::memcpy(s.in.a8, op.A.data(), sizeof(s.in.a8));
+        std::memcpy(s.in.b8, op.B.data(), sizeof(s.in.b8));
+        std::memcpy(s.in.g8, op.ref.data(), sizeof(s.in.g8));
+    }
+    if (kinds & (1u << SK_MX_FP8)) {
+        LowpOperands op = lowp_exact_operands(FMT_E4M3, true, LOWP_SEED_MX_FP8);
+        std::memcpy(s.in.amx8, op.A.data(), sizeof(s.in.amx8));
+        std::memcpy(s.in.bmx8, op.B.data(), sizeof(s.in.bmx8));
+        std::memcpy(s.in.samx8, op.SA.data(), sizeof(s.in.samx8));
+        std::memcpy(s.in.sbmx8, op.SB.data(), sizeof(s.in.sbmx8));
+        std::memcpy(s.in.gmx8, op.ref.data(), sizeof(s.in.gmx8));
+    }
+    if (kinds & (1u << SK_MX_FP4)) {
+        LowpOperands op = lowp_exact_operands(FMT_E2M1, true, LOWP_SEED_MX_FP4);
+        std::memcpy(s.in.amx4, op.A.data(), sizeof(s.in.amx4));
+        std::memcpy(s.in.bmx4, op.B.data(), sizeof(s.in.bmx4));
+        std::memcpy(s.in.samx4, op.SA.data(), sizeof(s.in.samx4));
+        std::memcpy(s.in.sbmx4, op.SB.data(), sizeof(s.in.sbmx4));
+        std::memcpy(s.in.gmx4, op.ref.data(), sizeof(s.in.gmx4));
+    }
+}
+
+struct SweepLaunch {
+    std::vector<uint32_t> records;
+    int blocks = 0, waves_per_block = 0;
+    size_t lds_bytes = 0;
+    bool exclusive = false;
+    float ms = 0;
+};
+
+// The largest LDS allocation one block may ask for, capped at a whole CU's.
+size_t sweep_lds_limit(int dev) {
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    size_t limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
+    limit = std::min(limit, CU_LDS_BYTES);
+    return limit / SWEEP_LDS_GRANULE * SWEEP_LDS_GRANULE;
+}
+
+// One launch of unit_sweep. More than half a CU's LDS per block makes the
+// blocks exclusive; if the device grants no more than that, or refuses the
+// large launch, the sweep runs on 64 KiB blocks, as many as fit the chip at
+// once, with exclusive = false, and the coverage numbers speak for themselves.
+SweepLaunch sweep_launch(int dev, const SweepSetup& setup, SweepParams p, int blocks_arg,
+                         int threads) {
+    const size_t fallback = 64 << 10;
+    size_t lds = sweep_lds_limit(dev);
+    require(lds >= SWEEP_LDS_GRANULE, "device reports no usable LDS");
+    bool exclusive = lds > CU_LDS_BYTES / 2;
+    if (exclusive && lds > fallback &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(unit_sweep),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess) {
+        (void)hipGetLastError();   // refused: not sticky
+        lds = fallback;
+        exclusive = false;
+    }
+    if (!exclusive) lds = std::min(lds, fallback);
+
+    DevBuf d_in(sizeof(SweepInputs));
+    HIP_CHECK(hipMemcpy(d_in.p, &setup.in, sizeof(SweepInputs), hipMemcpyHostToDevice));
+    const int cus = compute_units(dev);
+    Event t0, t1;
+    SweepLaunch out;
+    for (;;) {
+        int blocks = blocks_arg > 0 ? blocks_arg
+                                    : std::min(SWEEP_MAX_BLOCKS, cus * (int)(CU_LDS_BYTES / lds));
+        int wpb = threads / WAVE;
+        size_t n_words = (size_t)blocks * wpb * SWEEP_RECORD_WORDS;
+        DevBuf d_rec(n_words * 4);
+        // an unwritten record reads as all ones: no valid XCD, every counter bad
+        HIP_CHECK(hipMemset(d_rec.p, 0xff, n_words * 4));
+        p.lds_words = (uint32_t)(lds / 4);
+        HIP_CHECK(hipEventRecord(t0.e));
+        hipLaunchKernelGGL(unit_sweep, dim3(blocks), dim3(threads), lds, 0,
+                           d_in.as<const SweepInputs>(), p, d_rec.as<uint32_t>());
+        hipError_t launched = hipGetLastError();
+        if (launched != hipSuccess && exclusive) {
+            // the large-LDS launch was refused before anything ran
+            lds = fallback;
+            exclusive = false;
+            continue;
+        }
+        HIP_CHECK(launched);
+        HIP_CHECK(hipEventRecord(t1.e));
+        HIP_CHECK(hipEventSynchronize(t1.e));
+        HIP_CHECK(hipEventElapsedTime(&out.ms, t0.e, t1.e));
+        HIP_CHECK(hipDeviceSynchronize());
+        out.records.resize(n_words);
+        HIP_CHECK(hipMemcpy(out.records.data(), d_rec.p, n_words * 4, hipMemcpyDeviceToHost));
+        out.blocks = blocks;
+        out.waves_per_block = wpb;
+        out.lds_bytes = lds;
+        out.exclusive = exclusive;
+        return out;
+    }
+}
+
+py::dict sweep_golden_dict(uint32_t kinds, const SweepSetup& setup) {
+    py::dict g;
+    for (int k = 0; k < SK_COUNT; k++)
+        if (kinds >> k & 1) g[SWEEP_KIND_NAMES[k]] = setup.golden_ok[k];
+    return g;
+}
+
+// Raw entry point: one launch, no retries.
+py::dict unit_sweep_run(int dev, const std::vector<std::string>& kinds, int reps, int blocks,
+                        const py::object& poison, int threads) {
+    require(dev >= 0, "dev must be >= 0");
+    uint32_t mask = sweep_kind_mask(kinds);
+    require(reps >= 1 && reps <= SWEEP_MAX_REPS, "reps must be in 1..2^20");
+    require(blocks >= 0 && blocks <= SWEEP_MAX_BLOCKS, "blocks must be in 0..4096");
+    require(threads == 256 || threads == 512 || threads == 1024,
+            "threads must be 256, 512 or 1024");
+    SweepParams p{};
+    sweep_parse_poison(poison, mask, p);
+    HIP_CHECK(hipSetDevice(dev));
+    SweepSetup setup;
+    sweep_prepare(mask, setup);
+    p.kinds = setup.kinds;
+    p.reps = reps;
+    SweepLaunch r = sweep_launch(dev, setup, p, blocks, threads);
+    py::dict d;
+    d["records"] = as_bytes(r.records);
+    d["waves_per_block"] = r.waves_per_block;
+    d["blocks"] = r.blocks;
+    d["lds_bytes_per_block"] = (uint64_t)r.lds_bytes;
+    d["exclusive"] = r.exclusive;
+    d["golden_ok"] = sweep_golden_dict(mask, setup);
+    d["sweep_ms"] = r.ms;
+    d["reps"] = reps;
+    return d;
+}
+
+// Distinct (XCD, CU key, SIMD) triples in the records: HW_ID bits 15:8 are
+// the CU key, bits 5:4 the SIMD, XCC_ID bits 3:0 the XCD.
+size_t sweep_simds_seen(const std::vector<uint32_t>& records) {
+    std::vector<uint32_t> keys;
+    for (size_t i = 0; i + 1 < records.size(); i += SWEEP_RECORD_WORDS)
+        keys.push_back((records[i + 1] & 15u) << 10 | (records[i] >> 8 & 255u) << 2 |
+                       (records[i] >> 4 & 3u));
+    std::sort(keys.begin(), keys.end());
+    return std::unique(keys.begin(), keys.end()) - keys.begin();
+}
+
+// What probe_device calls: the sweep, launched again (three launches at most)
+// only while the merged records do not cover 4 SIMDs on every CU. A HIP error
+// propagates; nothing is relaunched after one.
+py::dict unit_sweep_probe(int dev, bool low_precision, int reps) {
+    require(dev >= 0, "dev must be >= 0");
+    require(reps >= 1 && reps <= SWEEP_MAX_REPS, "reps must be in 1..2^20");
+    uint32_t mask = 1u << SK_F32 | 1u << SK_BF16 | 1u << SK_LDS;
+    if (low_precision) mask |= 1u << SK_FP8 | 1u << SK_MX_FP8 | 1u << SK_MX_FP4;
+    HIP_CHECK(hipSetDevice(dev));
+    SweepSetup setup;
+    sweep_prepare(mask, setup);
+    SweepParams p{};
+    p.poison_kind = -1;
+    p.kinds = setup.kinds;
+    p.reps = reps;
+    const size_t expected = (size_t)compute_units(dev) * 4;
+    std::vector<uint32_t> merged;
+    SweepLaunch last;
+    float total_ms = 0;
+    int launches = 0;
+    bool exclusive = true;
+    while (launches < SWEEP_MAX_LAUNCHES) {
+        last = sweep_launch(dev, setup, p, 0, SWEEP_THREADS);
+        launches++;
+        total_ms += last.ms;
+        exclusive = exclusive && last.exclusive;
+        merged.insert(merged.end(), last.records.begin(), last.records.end());
+        if (sweep_simds_seen(merged) >= expected) break;
+    }
+    py::dict d;
+    d["records"] = as_bytes(merged);
+    d["waves_per_block"] = last.waves_per_block;
+    d["blocks"] = last.blocks;
+    d["lds_bytes_per_block"] = (uint64_t)last.lds_bytes;
+    d["exclusive"] = exclusive;
+    d["golden_ok"] = sweep_golden_dict(mask, setup);
+    d["sweep_ms"] = total_ms;
+    d["reps"] = reps;
+    d["launches"] = launches;
     return d;
 }
 
@@ -1300,4 +1873,10 @@ PYBIND11_MODULE(_gpuprobe, m) {
           py::arg("iters") = 64, py::arg("blocks") = 0);
     m.def("mfma_probe_lowp", &mfma_probe_lowp, py::arg("dev") = 0,
           py::arg("burn_iters") = 20000);
+    m.def("unit_sweep_run", &unit_sweep_run, py::arg("dev"), py::arg("kinds"),
+          py::arg("reps"), py::arg("blocks") = 0, py::arg("poison") = py::none(),
+          py::arg("threads") = SWEEP_THREADS);
+    m.def("unit_sweep_probe", &unit_sweep_probe, py::arg("dev") = 0,
+          py::arg("low_precision") = false, py::arg("reps") = SWEEP_DEFAULT_REPS);
+    m.attr("UNIT_SWEEP_DEFAULT_REPS") = SWEEP_DEFAULT_REPS;
 }
