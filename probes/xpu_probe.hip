@@ -641,18 +641,98 @@ void require(bool cond, const char* what) {
     if (!cond) throw std::invalid_argument(what);
 }
 
+void require_dev(int dev) { require(dev >= 0, "dev must be >= 0"); }
+
 constexpr int MAX_TILE_BLOCKS = 4096;   // 16 MiB of bf16-tile slabs at most
 constexpr int MAX_BURN_BLOCKS = 65536;  // 64 MiB of burn output at most
 
-// Device allocation that is freed on every path, exceptions included.
+void require_tile_blocks(int blocks) {
+    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
+}
+
+// 0 asks for the entry point's own per-CU default (burn_blocks).
+void require_burn_blocks(int blocks) {
+    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
+}
+
+// "e4m3" / "e5m2" / "e2m1" → the instruction's format number, if the entry
+// point allows that format.
+int parse_fmt(const std::string& s, std::initializer_list<int> allowed, const char* what) {
+    int f = s == "e4m3" ? FMT_E4M3 : s == "e5m2" ? FMT_E5M2 : s == "e2m1" ? FMT_E2M1 : -1;
+    require(std::find(allowed.begin(), allowed.end(), f) != allowed.end(), what);
+    return f;
+}
+
+// Device memory, pinned host memory and events that are released on every
+// path, exceptions included.
 struct DevBuf {
     void* p = nullptr;
     explicit DevBuf(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
     ~DevBuf() { if (p) (void)hipFree(p); }
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+struct HostBuf {
+    void* p = nullptr;
+    explicit HostBuf(size_t bytes) { HIP_CHECK(hipHostMalloc(&p, bytes)); }
+    ~HostBuf() { if (p) (void)hipHostFree(p); }
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIP_CHECK(hipEventCreate(&e)); }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+};
+
+// A device copy of `bytes` bytes at `src`.
+DevBuf upload(const void* src, size_t bytes) {
+    DevBuf d(bytes);
+    HIP_CHECK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return d;
+}
+
+// Milliseconds the device spent on what `enqueue` puts on the null stream:
+// one kernel launch or one async copy, and nothing else. A refused launch is
+// reported once the closing event is recorded, outside the timed window.
+template <class F>
+float timed_ms(F&& enqueue) {
+    Event t0, t1;
+    HIP_CHECK(hipEventRecord(t0.e));
+    enqueue();
+    HIP_CHECK(hipEventRecord(t1.e));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventSynchronize(t1.e));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
+    return ms;
+}
+
+template <class F>
+float best_timed_ms(int iters, F&& enqueue) {
+    float best = 1e30f;
+    for (int i = 0; i < iters; i++) best = std::min(best, timed_ms(enqueue));
+    return best;
+}
+
+// `launch(out)` starts one kernel that writes `n` floats at `out`; they come
+// back once it has run.
+template <class F>
+std::vector<float> launch_fetch(size_t n, F&& launch) {
+    DevBuf out(n * 4);
+    launch(out.as<float>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<float> h(n);
+    HIP_CHECK(hipMemcpy(h.data(), out.p, n * 4, hipMemcpyDeviceToHost));
+    return h;
+}
 
 int compute_units(int dev) {
     hipDeviceProp_t prop;
@@ -695,7 +775,7 @@ int device_count() {
 }
 
 py::dict device_info(int dev) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     size_t free_b = 0, total_b = 0;
@@ -716,20 +796,17 @@ py::dict device_info(int dev) {
 
 constexpr uint64_t PATTERN_SALT = 0xA5A5A5A55A5A5A5Aull;
 
-// Pattern-checked copy: fill src with the memtest address pattern, clear dst,
-// run copy_f4 and count the 64-bit words of dst that do not hold the pattern.
-// The pattern differs at every word, so a copy from the wrong index, a
-// skipped element or a short loop bound all show up in the count.
-uint64_t checked_copy(float4* src, float4* dst, size_t n4, int blocks) {
-    size_t n = n4 * 2;  // 64-bit words
+// Fill the `n` 64-bit words at `w` with the memtest address pattern, run
+// `between`, and count the words at `r` that do not hold the pattern.
+template <class F>
+uint64_t pattern_mismatches(uint64_t* w, const uint64_t* r, size_t n, int blocks,
+                            F&& between) {
     DevBuf mm(sizeof(unsigned long long));
     HIP_CHECK(hipMemset(mm.p, 0, sizeof(unsigned long long)));
-    HIP_CHECK(hipMemset(dst, 0, n4 * sizeof(float4)));
-    hipLaunchKernelGGL(pattern_write, dim3(blocks), dim3(256), 0, 0,
-                       (uint64_t*)src, n, PATTERN_SALT);
-    hipLaunchKernelGGL(copy_f4, dim3(blocks), dim3(256), 0, 0, src, dst, n4);
-    hipLaunchKernelGGL(pattern_check, dim3(blocks), dim3(256), 0, 0,
-                       (const uint64_t*)dst, n, PATTERN_SALT,
+    hipLaunchKernelGGL(pattern_write, dim3(blocks), dim3(256), 0, 0, w, n, PATTERN_SALT);
+    HIP_CHECK(hipGetLastError());
+    between();
+    hipLaunchKernelGGL(pattern_check, dim3(blocks), dim3(256), 0, 0, r, n, PATTERN_SALT,
                        mm.as<unsigned long long>());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
@@ -738,8 +815,24 @@ uint64_t checked_copy(float4* src, float4* dst, size_t n4, int blocks) {
     return mismatches;
 }
 
+void launch_copy(int blocks, const float4* src, float4* dst, size_t n4) {
+    hipLaunchKernelGGL(copy_f4, dim3(blocks), dim3(256), 0, 0, src, dst, n4);
+}
+
+// Pattern-checked copy: fill src with the memtest address pattern, clear dst,
+// run copy_f4 and count the 64-bit words of dst that do not hold the pattern.
+// The pattern differs at every word, so a copy from the wrong index, a
+// skipped element or a short loop bound all show up in the count.
+uint64_t checked_copy(float4* src, float4* dst, size_t n4, int blocks) {
+    HIP_CHECK(hipMemset(dst, 0, n4 * sizeof(float4)));
+    return pattern_mismatches((uint64_t*)src, (const uint64_t*)dst, n4 * 2, blocks, [&] {
+        launch_copy(blocks, src, dst, n4);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 py::dict hbm_copy_check(int dev, size_t bytes) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(bytes >= sizeof(float4), "bytes must hold at least one float4 (16)");
     HIP_CHECK(hipSetDevice(dev));
     size_t n4 = bytes / sizeof(float4);
@@ -752,7 +845,7 @@ py::dict hbm_copy_check(int dev, size_t bytes) {
 }
 
 py::dict hbm_bandwidth_probe(int dev, size_t bytes, int iters) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(bytes >= sizeof(float4), "bytes must hold at least one float4 (16)");
     require(iters > 0, "iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
@@ -761,24 +854,11 @@ py::dict hbm_bandwidth_probe(int dev, size_t bytes, int iters) {
     float4 *src = src_buf.as<float4>(), *dst = dst_buf.as<float4>();
     HIP_CHECK(hipMemset(src, 0x3c, n4 * sizeof(float4)));
     int blocks = compute_units(dev) * 8;  // ≫256 WGs, fills all XCDs
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    // warmup
-    hipLaunchKernelGGL(copy_f4, dim3(blocks), dim3(256), 0, 0, src, dst, n4);
+    auto copy = [&] { launch_copy(blocks, src, dst, n4); };
+    copy();  // warmup
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
-    float best_ms = 1e30f;
-    for (int i = 0; i < iters; i++) {
-        HIP_CHECK(hipEventRecord(t0));
-        hipLaunchKernelGGL(copy_f4, dim3(blocks), dim3(256), 0, 0, src, dst, n4);
-        HIP_CHECK(hipEventRecord(t1));
-        HIP_CHECK(hipEventSynchronize(t1));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-        if (ms < best_ms) best_ms = ms;
-    }
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
+    float best_ms = best_timed_ms(iters, copy);
     // one pattern-checked copy after timing: the rate above says nothing
     // about whether dst ever equalled src
     uint64_t copy_mismatches = checked_copy(src, dst, n4, blocks);
@@ -807,23 +887,23 @@ int burn_blocks(int dev, int blocks, int per_cu) {
     return blocks > 0 ? blocks : compute_units(dev) * per_cu;
 }
 
+void launch_lds_burn(int blocks, float* out, int iters) {
+    hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out, iters);
+}
+
 py::bytes lds_read_burn_run(int dev, int iters, int blocks) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(iters > 0, "iters must be > 0");
-    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
+    require_burn_blocks(blocks);
     HIP_CHECK(hipSetDevice(dev));
     blocks = burn_blocks(dev, blocks, 4);
-    std::vector<float> h((size_t)blocks * 256);
-    DevBuf out(h.size() * 4);
-    hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out.as<float>(), iters);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
-    return as_bytes(h);
+    return as_bytes(launch_fetch((size_t)blocks * 256, [&](float* out) {
+        launch_lds_burn(blocks, out, iters);
+    }));
 }
 
 py::dict lds_bandwidth_probe(int dev, int iters) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(iters > 0, "iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     int blocks = burn_blocks(dev, 0, 4);   // 4 × 32 KiB per CU
@@ -831,22 +911,14 @@ py::dict lds_bandwidth_probe(int dev, int iters) {
     DevBuf out_buf(warm.size() * 4);
     float* out = out_buf.as<float>();
     static_assert(256 <= LDS_EXACT_ITERS, "warm-up sums must stay exact");
-    hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out, 256);
+    launch_lds_burn(blocks, out, 256);
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
-    // the warm-up launch doubles as the read-address check (exact sums)
+    // the warm-up launch doubles as the read-address check (exact sums); the
+    // timed launch reuses its buffer, so nothing is allocated in between
     HIP_CHECK(hipMemcpy(warm.data(), out, warm.size() * 4, hipMemcpyDeviceToHost));
     uint64_t mismatches = lds_mismatches(warm, 256);
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0));
-    hipLaunchKernelGGL(lds_read_burn, dim3(blocks), dim3(256), 0, 0, out, iters);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
+    float ms = timed_ms([&] { launch_lds_burn(blocks, out, iters); });
     // bytes: blocks × 256 lanes × 8 b128-reads × 16 B per iteration
     double bytes = (double)blocks * 256 * 8 * 16 * (double)iters;
     py::dict d;
@@ -857,7 +929,7 @@ py::dict lds_bandwidth_probe(int dev, int iters) {
 }
 
 py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(steps > 0, "steps must be > 0");
     // n >= 2 for the Sattolo loop below; indices are uint32_t
     require(bytes >= 8, "bytes must hold at least two uint32 (8)");
@@ -879,22 +951,15 @@ py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
     // the host holds the chain: where `steps` hops from 0 must end
     uint32_t expected = 0;
     for (int i = 0; i < steps; i++) expected = next[expected];
-    DevBuf next_buf(n * 4), out_buf(4);
+    DevBuf next_buf = upload(next.data(), n * 4), out_buf(4);
     uint32_t *d_next = next_buf.as<uint32_t>(), *d_out = out_buf.as<uint32_t>();
-    HIP_CHECK(hipMemcpy(d_next, next.data(), n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pointer_chase, dim3(1), dim3(64), 0, 0, d_next, d_out, 1000);
+    auto chase = [&](int hops) {
+        hipLaunchKernelGGL(pointer_chase, dim3(1), dim3(64), 0, 0, d_next, d_out, hops);
+    };
+    chase(1000);  // warmup
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0));
-    hipLaunchKernelGGL(pointer_chase, dim3(1), dim3(64), 0, 0, d_next, d_out, steps);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
+    float ms = timed_ms([&] { chase(steps); });
     uint32_t final_index = 0;
     HIP_CHECK(hipMemcpy(&final_index, d_out, 4, hipMemcpyDeviceToHost));
     py::dict d;
@@ -906,45 +971,27 @@ py::dict hbm_latency_probe(int dev, size_t bytes, int steps) {
 }
 
 py::dict pcie_bandwidth_probe(int dev, size_t bytes, int iters) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(bytes >= 1, "bytes must be >= 1");
     require(iters > 0, "iters must be > 0");
     // Host-link health: pinned-memory H2D/D2H streaming. MI355X host link
     // is PCIe Gen5 x16 (63 GB/s spec); a degraded link (wrong slot width,
     // retraining) shows up far below that.
     HIP_CHECK(hipSetDevice(dev));
-    void* host = nullptr;
-    void* d = nullptr;
-    HIP_CHECK(hipHostMalloc(&host, bytes));
-    HIP_CHECK(hipMalloc(&d, bytes));
-    std::memset(host, 0x5a, bytes);
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
+    HostBuf host(bytes);
+    DevBuf d(bytes);
+    std::memset(host.p, 0x5a, bytes);
     auto run = [&](bool h2d) {
-        // warmup
-        HIP_CHECK(hipMemcpyAsync(h2d ? d : host, h2d ? host : d, bytes,
-                                 h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, 0));
-        HIP_CHECK(hipDeviceSynchronize());
-        float best = 1e30f;
-        for (int i = 0; i < iters; i++) {
-            HIP_CHECK(hipEventRecord(t0));
-            HIP_CHECK(hipMemcpyAsync(h2d ? d : host, h2d ? host : d, bytes,
+        auto copy = [&] {
+            HIP_CHECK(hipMemcpyAsync(h2d ? d.p : host.p, h2d ? host.p : d.p, bytes,
                                      h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, 0));
-            HIP_CHECK(hipEventRecord(t1));
-            HIP_CHECK(hipEventSynchronize(t1));
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-            if (ms < best) best = ms;
-        }
-        return (double)bytes / (best * 1e6);
+        };
+        copy();  // warmup
+        HIP_CHECK(hipDeviceSynchronize());
+        return (double)bytes / (best_timed_ms(iters, copy) * 1e6);
     };
     double h2d = run(true);
     double d2h = run(false);
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(d));
-    HIP_CHECK(hipHostFree(host));
     py::dict r;
     r["h2d_gbps"] = h2d;
     r["d2h_gbps"] = d2h;
@@ -958,20 +1005,16 @@ py::dict pcie_bandwidth_probe(int dev, size_t bytes, int iters) {
 // Offsets outside the buffer are rejected, never accessed.
 py::dict memtest(int dev, size_t bytes, const std::vector<uint64_t>& corrupt_offsets,
                  uint64_t corrupt_xor) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(bytes >= sizeof(uint64_t), "bytes must hold at least one uint64 (8)");
     size_t n = bytes / sizeof(uint64_t);
     for (uint64_t off : corrupt_offsets)
         require(off < n, "corrupt_offsets entry is outside the buffer");
     HIP_CHECK(hipSetDevice(dev));
-    DevBuf buf_mem(n * sizeof(uint64_t)), mm_mem(sizeof(unsigned long long));
+    DevBuf buf_mem(n * sizeof(uint64_t));
     uint64_t* buf = buf_mem.as<uint64_t>();
-    unsigned long long* mm = mm_mem.as<unsigned long long>();
-    HIP_CHECK(hipMemset(mm, 0, sizeof(unsigned long long)));
-    uint64_t salt = PATTERN_SALT;
-    int blocks = compute_units(dev) * 8;
-    hipLaunchKernelGGL(pattern_write, dim3(blocks), dim3(256), 0, 0, buf, n, salt);
-    if (!corrupt_offsets.empty()) {
+    uint64_t mismatches = pattern_mismatches(buf, buf, n, compute_units(dev) * 8, [&] {
+        if (corrupt_offsets.empty()) return;
         HIP_CHECK(hipDeviceSynchronize());
         for (uint64_t off : corrupt_offsets) {
             uint64_t w = 0;
@@ -979,17 +1022,14 @@ py::dict memtest(int dev, size_t bytes, const std::vector<uint64_t>& corrupt_off
             w ^= corrupt_xor;
             HIP_CHECK(hipMemcpy(buf + off, &w, sizeof(w), hipMemcpyHostToDevice));
         }
-    }
-    hipLaunchKernelGGL(pattern_check, dim3(blocks), dim3(256), 0, 0, buf, n, salt, mm);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    unsigned long long mismatches = 0;
-    HIP_CHECK(hipMemcpy(&mismatches, mm, sizeof(mismatches), hipMemcpyDeviceToHost));
+    });
     py::dict d;
     d["bytes"] = (uint64_t)(n * sizeof(uint64_t));
-    d["mismatches"] = (uint64_t)mismatches;
+    d["mismatches"] = mismatches;
     return d;
 }
+
+// --- probe inputs --------------------------------------------------------------
 
 // Deterministic full-mantissa test value: random sign, 23 random mantissa
 // bits, exponent in [-4, 3].
@@ -1003,39 +1043,25 @@ float lcg_f32(uint64_t& s) {
     return f;
 }
 
-// One launch of mfma_f32_tile on `blocks` blocks → blocks × 256 floats.
-// C may be nullptr (zero accumulator).
-std::vector<float> run_f32_tile(const float* A, const float* B, const float* C,
-                                int blocks) {
-    std::vector<float> hD((size_t)blocks * 256);
-    DevBuf dA(64 * 4), dB(64 * 4), dC(256 * 4), dD(hD.size() * 4);
-    HIP_CHECK(hipMemcpy(dA.p, A, 64 * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB.p, B, 64 * 4, hipMemcpyHostToDevice));
-    if (C) HIP_CHECK(hipMemcpy(dC.p, C, 256 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_f32_tile, dim3(blocks), dim3(WAVE), 0, 0,
-                       dA.as<float>(), dB.as<float>(),
-                       C ? dC.as<float>() : (const float*)nullptr, dD.as<float>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
-    return hD;
+uint32_t lcg_bits(uint64_t& s) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(s >> 33);
 }
 
-py::bytes mfma_f32_tile_run(int dev, py::buffer A, py::buffer B, py::object C,
-                            int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
-    py::buffer_info ia = A.request(), ib = B.request();
-    const float* pa = (const float*)tile_buffer(ia, 4, 64, "A must be 16x4 contiguous f32");
-    const float* pb = (const float*)tile_buffer(ib, 4, 64, "B must be 4x16 contiguous f32");
-    py::buffer_info ic;
-    const float* pc = nullptr;
-    if (!C.is_none()) {
-        ic = py::cast<py::buffer>(C).request();
-        pc = (const float*)tile_buffer(ic, 4, 256, "C must be 16x16 contiguous f32");
-    }
-    HIP_CHECK(hipSetDevice(dev));
-    return as_bytes(run_f32_tile(pa, pb, pc, blocks));
+uint16_t bf16_round_bits(float x) {
+    // bf16 storage rounding (round-to-nearest-even on the top 16 bits)
+    uint32_t u;
+    std::memcpy(&u, &x, 4);
+    uint32_t lsb = (u >> 16) & 1u;
+    u += 0x7fffu + lsb;
+    return (uint16_t)(u >> 16);
+}
+
+float bf16_bits_to_float(uint16_t h) {
+    uint32_t u = (uint32_t)h << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
 }
 
 // The f32 probe's fixed tile: A (16×4), B (4×16) and the host's product.
@@ -1056,100 +1082,6 @@ void f32_probe_tile(std::vector<float>& hA, std::vector<float>& hB,
                 ref[i * 16 + j] = fmaf(hA[i * 4 + k], hB[k * 16 + j], ref[i * 16 + j]);
 }
 
-py::dict mfma_probe_f32(int dev) {
-    require(dev >= 0, "dev must be >= 0");
-    HIP_CHECK(hipSetDevice(dev));
-    std::vector<float> hA, hB, ref;
-    f32_probe_tile(hA, hB, ref);
-    // 2 blocks per CU: every CU's matrix cores run the tile
-    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    std::vector<float> hD = run_f32_tile(hA.data(), hB.data(), nullptr, blocks);
-    double max_abs_err = 0;
-    for (int i = 0; i < 256; i++) {
-        double e = std::fabs((double)hD[i] - (double)ref[i]);
-        if (std::isnan(e)) { max_abs_err = e; break; }   // std::max would drop it
-        max_abs_err = std::max(max_abs_err, e);
-    }
-    bool bits_equal = std::memcmp(hD.data(), ref.data(), 256 * 4) == 0;
-    uint64_t bad_slabs = slab_mismatches(hD, 256);
-    py::dict d;
-    d["max_abs_err"] = max_abs_err;   // exact f32 MFMA ⇒ expect 0.0
-    d["slab_mismatches"] = bad_slabs;
-    d["blocks"] = blocks;
-    d["ok"] = bits_equal && bad_slabs == 0;
-    return d;
-}
-
-static uint16_t bf16_round_bits(float x) {
-    // bf16 storage rounding (round-to-nearest-even on the top 16 bits)
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    uint32_t lsb = (u >> 16) & 1u;
-    u += 0x7fffu + lsb;
-    return (uint16_t)(u >> 16);
-}
-
-static float bf16_bits_to_float(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
-// One launch of mfma_bf16_tile on `blocks` blocks → blocks × 1024 floats.
-std::vector<float> run_bf16_tile(const uint16_t* A, const uint16_t* B, int blocks) {
-    std::vector<float> hD((size_t)blocks * 1024);
-    DevBuf dA(512 * 2), dB(512 * 2), dD(hD.size() * 4);
-    HIP_CHECK(hipMemcpy(dA.p, A, 512 * 2, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB.p, B, 512 * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_bf16_tile, dim3(blocks), dim3(WAVE), 0, 0,
-                       dA.as<const __bf16>(), dB.as<const __bf16>(), dD.as<float>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
-    return hD;
-}
-
-py::bytes mfma_bf16_tile_run(int dev, py::buffer A_bits, py::buffer B_bits, int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
-    py::buffer_info ia = A_bits.request(), ib = B_bits.request();
-    const uint16_t* pa = (const uint16_t*)tile_buffer(
-        ia, 2, 512, "A_bits must be 32x16 contiguous uint16");
-    const uint16_t* pb = (const uint16_t*)tile_buffer(
-        ib, 2, 512, "B_bits must be 16x32 contiguous uint16");
-    HIP_CHECK(hipSetDevice(dev));
-    return as_bytes(run_bf16_tile(pa, pb, blocks));
-}
-
-// Output elements whose bits differ from lane (i & 63) of block 0's wave 0.
-// Every wave of the burn computes the same 64 values.
-uint64_t burn_mismatches(const std::vector<float>& out) {
-    uint64_t bad = 0;
-    for (size_t i = WAVE; i < out.size(); i++)
-        if (std::memcmp(&out[i], &out[i & (WAVE - 1)], 4) != 0) bad++;
-    return bad;
-}
-
-py::dict mfma_bf16_burn_run(int dev, int iters, int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    require(iters > 0, "iters must be > 0");
-    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
-    HIP_CHECK(hipSetDevice(dev));
-    blocks = burn_blocks(dev, blocks, 2);
-    std::vector<float> h((size_t)blocks * 256);
-    DevBuf out(h.size() * 4);
-    hipLaunchKernelGGL(mfma_bf16_burn, dim3(blocks), dim3(256), 0, 0, out.as<float>(), iters);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
-    py::dict d;
-    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
-    d["mismatches"] = burn_mismatches(h);
-    d["blocks"] = blocks;
-    return d;
-}
-
 // The bf16 probe's fixed tile inputs, as bf16 bit patterns: A (32×16) and
 // B (16×32), random values over 8 binades (all 8 significand bits in play).
 void bf16_probe_inputs(std::vector<uint16_t>& hA, std::vector<uint16_t>& hB) {
@@ -1160,227 +1092,7 @@ void bf16_probe_inputs(std::vector<uint16_t>& hA, std::vector<uint16_t>& hB) {
     for (uint16_t& v : hB) v = bf16_round_bits(lcg_f32(rng));
 }
 
-// Each bf16×bf16 product is exact in f32 and the 16 additions lose at most
-// one ulp each in any order, so |D − ref| ≤ 16·2^-23·Σ|a·b| holds for a
-// healthy matrix core whatever its internal summation order; a mapping error
-// is O(1) relative. `D` is one 32×32 slab.
-bool bf16_tile_within_bound(const std::vector<uint16_t>& hA,
-                            const std::vector<uint16_t>& hB, const float* D,
-                            double& max_rel_err) {
-    bool tile_ok = true;
-    max_rel_err = 0;
-    for (int i = 0; i < 32; i++)
-        for (int j = 0; j < 32; j++) {
-            double ref = 0, mag = 0;
-            for (int k = 0; k < 16; k++) {
-                double p = (double)bf16_bits_to_float(hA[i * 16 + k]) *
-                           (double)bf16_bits_to_float(hB[k * 32 + j]);
-                ref += p;
-                mag += std::fabs(p);
-            }
-            double err = std::fabs((double)D[i * 32 + j] - ref);
-            if (!(err <= 16.0 * 0x1p-23 * mag)) tile_ok = false;   // NaN fails
-            if (!std::isnan(max_rel_err)) {
-                double rel = err / std::max(1.0, std::fabs(ref));
-                max_rel_err = std::isnan(rel) ? rel : std::max(max_rel_err, rel);
-            }
-        }
-    return tile_ok;
-}
-
-py::dict mfma_probe_bf16(int dev, int burn_iters) {
-    require(dev >= 0, "dev must be >= 0");
-    require(burn_iters > 0, "burn_iters must be > 0");
-    HIP_CHECK(hipSetDevice(dev));
-    // --- correctness tile ---
-    std::vector<uint16_t> hA, hB;
-    bf16_probe_inputs(hA, hB);
-    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    std::vector<float> hD = run_bf16_tile(hA.data(), hB.data(), blocks);
-    double max_rel_err = 0;
-    bool tile_ok = bf16_tile_within_bound(hA, hB, hD.data(), max_rel_err);
-    uint64_t bad_slabs = slab_mismatches(hD, 1024);
-
-    // --- throughput burn ---
-    int burn_grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
-    std::vector<float> h_out((size_t)burn_grid * 256);
-    DevBuf out_buf(h_out.size() * 4);
-    float* out = out_buf.as<float>();
-    hipLaunchKernelGGL(mfma_bf16_burn, dim3(burn_grid), dim3(256), 0, 0, out, 64);
-    HIP_CHECK(hipDeviceSynchronize());
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0));
-    hipLaunchKernelGGL(mfma_bf16_burn, dim3(burn_grid), dim3(256), 0, 0, out, burn_iters);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
-    // the timed burn covers every CU; all waves must agree bit for bit
-    HIP_CHECK(hipMemcpy(h_out.data(), out, h_out.size() * 4, hipMemcpyDeviceToHost));
-    // FLOPs: blocks × 4 waves/WG × 4 acc × iters × 2·32·32·16
-    double flops = (double)burn_grid * 4.0 * 4.0 * burn_iters * 2.0 * 32 * 32 * 16;
-    py::dict d;
-    d["max_rel_err"] = max_rel_err;
-    d["slab_mismatches"] = bad_slabs;
-    d["burn_mismatches"] = burn_mismatches(h_out);
-    d["ok"] = tile_ok && bad_slabs == 0;
-    d["tflops"] = flops / (ms * 1e9);
-    d["burn_ms"] = ms;
-    return d;
-}
-
-// --- FP8 / MX -----------------------------------------------------------------
-
-// "e4m3" / "e5m2" / "e2m1" → the instruction's format number.
-int parse_fmt(const std::string& s, bool allow_fp4, const char* what) {
-    if (s == "e4m3") return FMT_E4M3;
-    if (s == "e5m2") return FMT_E5M2;
-    if (allow_fp4 && s == "e2m1") return FMT_E2M1;
-    throw std::invalid_argument(what);
-}
-
-// A C-contiguous buffer of exactly `count` unsigned bytes.
-const uint8_t* code_buffer(const py::buffer_info& info, size_t count, const char* what) {
-    require(info.format == py::format_descriptor<uint8_t>::format(), what);
-    return (const uint8_t*)tile_buffer(info, 1, count, what);
-}
-
-using fp8_kernel_t = void (*)(const uint8_t*, const uint8_t*, float*);
-using mx_kernel_t = void (*)(const uint8_t*, const uint8_t*, const uint8_t*,
-                             const uint8_t*, float*);
-
-fp8_kernel_t fp8_kernel(int af, int bf) {
-    if (af == FMT_E4M3) return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E4M3, FMT_E4M3>
-                                              : mfma_fp8_tile<FMT_E4M3, FMT_E5M2>;
-    return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E5M2, FMT_E4M3>
-                          : mfma_fp8_tile<FMT_E5M2, FMT_E5M2>;
-}
-
-// cbsz and blgp are immediates, so each format pair is its own kernel.
-template <int AF>
-mx_kernel_t mx_kernel_b(int bf) {
-    switch (bf) {
-        case FMT_E4M3: return mfma_mx_tile<AF, FMT_E4M3>;
-        case FMT_E5M2: return mfma_mx_tile<AF, FMT_E5M2>;
-        default:       return mfma_mx_tile<AF, FMT_E2M1>;
-    }
-}
-
-mx_kernel_t mx_kernel(int af, int bf) {
-    switch (af) {
-        case FMT_E4M3: return mx_kernel_b<FMT_E4M3>(bf);
-        case FMT_E5M2: return mx_kernel_b<FMT_E5M2>(bf);
-        default:       return mx_kernel_b<FMT_E2M1>(bf);
-    }
-}
-
-// One launch of mfma_fp8_tile on `blocks` blocks → blocks × 256 floats.
-std::vector<float> run_fp8_tile(const uint8_t* A, const uint8_t* B, int af, int bf,
-                                int blocks) {
-    std::vector<float> hD((size_t)blocks * 256);
-    DevBuf dA(512), dB(512), dD(hD.size() * 4);
-    HIP_CHECK(hipMemcpy(dA.p, A, 512, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB.p, B, 512, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(fp8_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
-                       dA.as<const uint8_t>(), dB.as<const uint8_t>(), dD.as<float>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
-    return hD;
-}
-
-// One launch of mfma_mx_tile on `blocks` blocks → blocks × 256 floats.
-std::vector<float> run_mx_tile(const uint8_t* A, const uint8_t* B, const uint8_t* SA,
-                               const uint8_t* SB, int af, int bf, int blocks) {
-    std::vector<float> hD((size_t)blocks * 256);
-    DevBuf dA(2048), dB(2048), dSA(64), dSB(64), dD(hD.size() * 4);
-    HIP_CHECK(hipMemcpy(dA.p, A, 2048, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB.p, B, 2048, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dSA.p, SA, 64, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dSB.p, SB, 64, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mx_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
-                       dA.as<const uint8_t>(), dB.as<const uint8_t>(),
-                       dSA.as<const uint8_t>(), dSB.as<const uint8_t>(), dD.as<float>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hD.data(), dD.p, hD.size() * 4, hipMemcpyDeviceToHost));
-    return hD;
-}
-
-py::bytes mfma_fp8_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
-                            const std::string& a_fmt, const std::string& b_fmt,
-                            int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
-    int af = parse_fmt(a_fmt, false, "a_fmt must be 'e4m3' or 'e5m2'");
-    int bf = parse_fmt(b_fmt, false, "b_fmt must be 'e4m3' or 'e5m2'");
-    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
-    const uint8_t* pa = code_buffer(ia, 512, "A_codes must be 16x32 contiguous uint8");
-    const uint8_t* pb = code_buffer(ib, 512, "B_codes must be 32x16 contiguous uint8");
-    HIP_CHECK(hipSetDevice(dev));
-    return as_bytes(run_fp8_tile(pa, pb, af, bf, blocks));
-}
-
-py::bytes mfma_mx_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
-                           py::buffer A_scales, py::buffer B_scales,
-                           const std::string& a_fmt, const std::string& b_fmt,
-                           int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
-    int af = parse_fmt(a_fmt, true, "a_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
-    int bf = parse_fmt(b_fmt, true, "b_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
-    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
-    py::buffer_info isa = A_scales.request(), isb = B_scales.request();
-    const uint8_t* pa = code_buffer(ia, 2048, "A_codes must be 16x128 contiguous uint8");
-    const uint8_t* pb = code_buffer(ib, 2048, "B_codes must be 128x16 contiguous uint8");
-    const uint8_t* psa = code_buffer(isa, 64, "A_scales must be 16x4 contiguous uint8");
-    const uint8_t* psb = code_buffer(isb, 64, "B_scales must be 4x16 contiguous uint8");
-    for (int i = 0; i < 2048; i++) {
-        require(af != FMT_E2M1 || pa[i] < 16, "A_codes: an e2m1 code must be below 16");
-        require(bf != FMT_E2M1 || pb[i] < 16, "B_codes: an e2m1 code must be below 16");
-    }
-    HIP_CHECK(hipSetDevice(dev));
-    return as_bytes(run_mx_tile(pa, pb, psa, psb, af, bf, blocks));
-}
-
-void launch_mx_burn(int fmt, int blocks, float* out, int iters) {
-    if (fmt == FMT_E2M1)
-        hipLaunchKernelGGL(mfma_mx_burn<FMT_E2M1>, dim3(blocks), dim3(256), 0, 0, out, iters);
-    else
-        hipLaunchKernelGGL(mfma_mx_burn<FMT_E4M3>, dim3(blocks), dim3(256), 0, 0, out, iters);
-}
-
-int parse_burn_fmt(const std::string& s) {
-    if (s == "e4m3") return FMT_E4M3;
-    if (s == "e2m1") return FMT_E2M1;
-    throw std::invalid_argument("fmt must be 'e4m3' or 'e2m1'");
-}
-
-py::dict mfma_mx_burn_run(int dev, const std::string& fmt, int iters, int blocks) {
-    require(dev >= 0, "dev must be >= 0");
-    int f = parse_burn_fmt(fmt);
-    require(iters > 0, "iters must be > 0");
-    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
-    HIP_CHECK(hipSetDevice(dev));
-    blocks = burn_blocks(dev, blocks, 2);
-    std::vector<float> h((size_t)blocks * 256);
-    DevBuf out(h.size() * 4);
-    launch_mx_burn(f, blocks, out.as<float>(), iters);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(h.data(), out.p, h.size() * 4, hipMemcpyDeviceToHost));
-    py::dict d;
-    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
-    d["mismatches"] = burn_mismatches(h);
-    d["blocks"] = blocks;
-    return d;
-}
-
-// Host decoders for the probe's reference (finite codes only).
+// Host decoders for the low-precision reference (finite codes only).
 double decode_fp8(uint8_t c, int ebits) {
     int mbits = 7 - ebits, bias = (1 << (ebits - 1)) - 1;
     int e = (c >> mbits) & ((1 << ebits) - 1), m = c & ((1 << mbits) - 1);
@@ -1398,11 +1110,6 @@ double decode_code(uint8_t c, int fmt) {
     return fmt == FMT_E2M1 ? decode_e2m1(c) : decode_fp8(c, fmt == FMT_E4M3 ? 4 : 5);
 }
 
-uint32_t lcg_bits(uint64_t& s) {
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(s >> 33);
-}
-
 // Exact-tile operand code: e4m3 with random sign and mantissa and exponent
 // field 6..9 (|v| in [0.5, 7.5], step 2^-4 at the least), or any e2m1 code.
 uint8_t exact_code(uint64_t& rng, int fmt) {
@@ -1410,11 +1117,6 @@ uint8_t exact_code(uint64_t& rng, int fmt) {
     if (fmt == FMT_E2M1) return (uint8_t)(r & 15);
     return (uint8_t)((r & 0x87) | (6 + ((r >> 8) & 3)) << 3);
 }
-
-struct LowpTile {
-    bool ok;
-    uint64_t bad_slabs;
-};
 
 struct LowpOperands {
     std::vector<uint8_t> A, B, SA, SB;   // codes (16×K, K×16) and E8M0 scales
@@ -1463,44 +1165,328 @@ LowpOperands lowp_exact_operands(int fmt, bool mx, uint64_t seed) {
     return op;
 }
 
-// The exact tile above on `blocks` blocks: slab 0 against the host, every
-// other slab against slab 0.
+// --- f32 / bf16 ----------------------------------------------------------------
+
+// One launch of mfma_f32_tile on `blocks` blocks → blocks × 256 floats.
+// C may be nullptr (zero accumulator).
+std::vector<float> run_f32_tile(const float* A, const float* B, const float* C,
+                                int blocks) {
+    DevBuf dA = upload(A, 64 * 4), dB = upload(B, 64 * 4), dC(256 * 4);
+    if (C) HIP_CHECK(hipMemcpy(dC.p, C, 256 * 4, hipMemcpyHostToDevice));
+    return launch_fetch((size_t)blocks * 256, [&](float* dD) {
+        hipLaunchKernelGGL(mfma_f32_tile, dim3(blocks), dim3(WAVE), 0, 0,
+                           dA.as<float>(), dB.as<float>(),
+                           C ? dC.as<float>() : (const float*)nullptr, dD);
+    });
+}
+
+py::bytes mfma_f32_tile_run(int dev, py::buffer A, py::buffer B, py::object C,
+                            int blocks) {
+    require_dev(dev);
+    require_tile_blocks(blocks);
+    py::buffer_info ia = A.request(), ib = B.request();
+    const float* pa = (const float*)tile_buffer(ia, 4, 64, "A must be 16x4 contiguous f32");
+    const float* pb = (const float*)tile_buffer(ib, 4, 64, "B must be 4x16 contiguous f32");
+    py::buffer_info ic;
+    const float* pc = nullptr;
+    if (!C.is_none()) {
+        ic = py::cast<py::buffer>(C).request();
+        pc = (const float*)tile_buffer(ic, 4, 256, "C must be 16x16 contiguous f32");
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_f32_tile(pa, pb, pc, blocks));
+}
+
+py::dict mfma_probe_f32(int dev) {
+    require_dev(dev);
+    HIP_CHECK(hipSetDevice(dev));
+    std::vector<float> hA, hB, ref;
+    f32_probe_tile(hA, hB, ref);
+    // 2 blocks per CU: every CU's matrix cores run the tile
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    std::vector<float> hD = run_f32_tile(hA.data(), hB.data(), nullptr, blocks);
+    double max_abs_err = 0;
+    for (int i = 0; i < 256; i++) {
+        double e = std::fabs((double)hD[i] - (double)ref[i]);
+        if (std::isnan(e)) { max_abs_err = e; break; }   // std::max would drop it
+        max_abs_err = std::max(max_abs_err, e);
+    }
+    bool bits_equal = std::memcmp(hD.data(), ref.data(), 256 * 4) == 0;
+    uint64_t bad_slabs = slab_mismatches(hD, 256);
+    py::dict d;
+    d["max_abs_err"] = max_abs_err;   // exact f32 MFMA ⇒ expect 0.0
+    d["slab_mismatches"] = bad_slabs;
+    d["blocks"] = blocks;
+    d["ok"] = bits_equal && bad_slabs == 0;
+    return d;
+}
+
+// One launch of mfma_bf16_tile on `blocks` blocks → blocks × 1024 floats.
+std::vector<float> run_bf16_tile(const uint16_t* A, const uint16_t* B, int blocks) {
+    DevBuf dA = upload(A, 512 * 2), dB = upload(B, 512 * 2);
+    return launch_fetch((size_t)blocks * 1024, [&](float* dD) {
+        hipLaunchKernelGGL(mfma_bf16_tile, dim3(blocks), dim3(WAVE), 0, 0,
+                           dA.as<const __bf16>(), dB.as<const __bf16>(), dD);
+    });
+}
+
+py::bytes mfma_bf16_tile_run(int dev, py::buffer A_bits, py::buffer B_bits, int blocks) {
+    require_dev(dev);
+    require_tile_blocks(blocks);
+    py::buffer_info ia = A_bits.request(), ib = B_bits.request();
+    const uint16_t* pa = (const uint16_t*)tile_buffer(
+        ia, 2, 512, "A_bits must be 32x16 contiguous uint16");
+    const uint16_t* pb = (const uint16_t*)tile_buffer(
+        ib, 2, 512, "B_bits must be 16x32 contiguous uint16");
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_bf16_tile(pa, pb, blocks));
+}
+
+// Output elements whose bits differ from lane (i & 63) of block 0's wave 0.
+// Every wave of the burn computes the same 64 values.
+uint64_t burn_mismatches(const std::vector<float>& out) {
+    uint64_t bad = 0;
+    for (size_t i = WAVE; i < out.size(); i++)
+        if (std::memcmp(&out[i], &out[i & (WAVE - 1)], 4) != 0) bad++;
+    return bad;
+}
+
+// The burns share a launcher shape, launch(blocks, out, iters): `blocks`
+// 256-thread workgroups that write blocks × 256 floats at `out`.
+
+// What the raw burn entry points return: one launch, no warm-up.
+template <class F>
+py::dict raw_burn(F&& launch, int blocks, int iters) {
+    std::vector<float> h = launch_fetch((size_t)blocks * 256, [&](float* out) {
+        launch(blocks, out, iters);
+    });
+    py::dict d;
+    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
+    d["mismatches"] = burn_mismatches(h);
+    d["blocks"] = blocks;
+    return d;
+}
+
+struct TimedBurn {
+    double tflops;
+    float ms;
+    uint64_t mismatches;
+};
+
+// What the probes run: a warm-up launch of 64 iterations, one timed launch of
+// `iters` on the same buffer, and the check that all its waves agree bit for
+// bit. `flops` is per block and iteration.
+template <class F>
+TimedBurn timed_burn(F&& launch, int blocks, int iters, double flops) {
+    std::vector<float> h((size_t)blocks * 256);
+    DevBuf out_buf(h.size() * 4);
+    float* out = out_buf.as<float>();
+    launch(blocks, out, 64);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    float ms = timed_ms([&] { launch(blocks, out, iters); });
+    HIP_CHECK(hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost));
+    return {(double)blocks * flops * iters / (ms * 1e9), ms, burn_mismatches(h)};
+}
+
+void launch_bf16_burn(int blocks, float* out, int iters) {
+    hipLaunchKernelGGL(mfma_bf16_burn, dim3(blocks), dim3(256), 0, 0, out, iters);
+}
+
+py::dict mfma_bf16_burn_run(int dev, int iters, int blocks) {
+    require_dev(dev);
+    require(iters > 0, "iters must be > 0");
+    require_burn_blocks(blocks);
+    HIP_CHECK(hipSetDevice(dev));
+    return raw_burn(launch_bf16_burn, burn_blocks(dev, blocks, 2), iters);
+}
+
+// Each bf16×bf16 product is exact in f32 and the 16 additions lose at most
+// one ulp each in any order, so |D − ref| ≤ 16·2^-23·Σ|a·b| holds for a
+// healthy matrix core whatever its internal summation order; a mapping error
+// is O(1) relative. `D` is one 32×32 slab.
+bool bf16_tile_within_bound(const std::vector<uint16_t>& hA,
+                            const std::vector<uint16_t>& hB, const float* D,
+                            double& max_rel_err) {
+    bool tile_ok = true;
+    max_rel_err = 0;
+    for (int i = 0; i < 32; i++)
+        for (int j = 0; j < 32; j++) {
+            double ref = 0, mag = 0;
+            for (int k = 0; k < 16; k++) {
+                double p = (double)bf16_bits_to_float(hA[i * 16 + k]) *
+                           (double)bf16_bits_to_float(hB[k * 32 + j]);
+                ref += p;
+                mag += std::fabs(p);
+            }
+            double err = std::fabs((double)D[i * 32 + j] - ref);
+            if (!(err <= 16.0 * 0x1p-23 * mag)) tile_ok = false;   // NaN fails
+            if (!std::isnan(max_rel_err)) {
+                double rel = err / std::max(1.0, std::fabs(ref));
+                max_rel_err = std::isnan(rel) ? rel : std::max(max_rel_err, rel);
+            }
+        }
+    return tile_ok;
+}
+
+py::dict mfma_probe_bf16(int dev, int burn_iters) {
+    require_dev(dev);
+    require(burn_iters > 0, "burn_iters must be > 0");
+    HIP_CHECK(hipSetDevice(dev));
+    // --- correctness tile ---
+    std::vector<uint16_t> hA, hB;
+    bf16_probe_inputs(hA, hB);
+    int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
+    std::vector<float> hD = run_bf16_tile(hA.data(), hB.data(), blocks);
+    double max_rel_err = 0;
+    bool tile_ok = bf16_tile_within_bound(hA, hB, hD.data(), max_rel_err);
+    uint64_t bad_slabs = slab_mismatches(hD, 1024);
+
+    // --- throughput burn: 2 × 256-thread WGs per CU, so it covers every CU ---
+    // FLOPs per block and iteration: 4 waves/WG × 4 acc × 2·32·32·16
+    TimedBurn burn = timed_burn(launch_bf16_burn, burn_blocks(dev, 0, 2), burn_iters,
+                                4.0 * 4.0 * 2.0 * 32 * 32 * 16);
+    py::dict d;
+    d["max_rel_err"] = max_rel_err;
+    d["slab_mismatches"] = bad_slabs;
+    d["burn_mismatches"] = burn.mismatches;
+    d["ok"] = tile_ok && bad_slabs == 0;
+    d["tflops"] = burn.tflops;
+    d["burn_ms"] = burn.ms;
+    return d;
+}
+
+// --- FP8 / MX -----------------------------------------------------------------
+
+// A C-contiguous buffer of exactly `count` unsigned bytes.
+const uint8_t* code_buffer(const py::buffer_info& info, size_t count, const char* what) {
+    require(info.format == py::format_descriptor<uint8_t>::format(), what);
+    return (const uint8_t*)tile_buffer(info, 1, count, what);
+}
+
+using fp8_kernel_t = void (*)(const uint8_t*, const uint8_t*, float*);
+using mx_kernel_t = void (*)(const uint8_t*, const uint8_t*, const uint8_t*,
+                             const uint8_t*, float*);
+
+fp8_kernel_t fp8_kernel(int af, int bf) {
+    if (af == FMT_E4M3) return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E4M3, FMT_E4M3>
+                                              : mfma_fp8_tile<FMT_E4M3, FMT_E5M2>;
+    return bf == FMT_E4M3 ? mfma_fp8_tile<FMT_E5M2, FMT_E4M3>
+                          : mfma_fp8_tile<FMT_E5M2, FMT_E5M2>;
+}
+
+// cbsz and blgp are immediates, so each format pair is its own kernel.
+template <int AF>
+mx_kernel_t mx_kernel_b(int bf) {
+    switch (bf) {
+        case FMT_E4M3: return mfma_mx_tile<AF, FMT_E4M3>;
+        case FMT_E5M2: return mfma_mx_tile<AF, FMT_E5M2>;
+        default:       return mfma_mx_tile<AF, FMT_E2M1>;
+    }
+}
+
+mx_kernel_t mx_kernel(int af, int bf) {
+    switch (af) {
+        case FMT_E4M3: return mx_kernel_b<FMT_E4M3>(bf);
+        case FMT_E5M2: return mx_kernel_b<FMT_E5M2>(bf);
+        default:       return mx_kernel_b<FMT_E2M1>(bf);
+    }
+}
+
+// One launch of mfma_fp8_tile on `blocks` blocks → blocks × 256 floats.
+std::vector<float> run_fp8_tile(const uint8_t* A, const uint8_t* B, int af, int bf,
+                                int blocks) {
+    DevBuf dA = upload(A, 512), dB = upload(B, 512);
+    return launch_fetch((size_t)blocks * 256, [&](float* dD) {
+        hipLaunchKernelGGL(fp8_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
+                           dA.as<const uint8_t>(), dB.as<const uint8_t>(), dD);
+    });
+}
+
+// One launch of mfma_mx_tile on `blocks` blocks → blocks × 256 floats.
+std::vector<float> run_mx_tile(const uint8_t* A, const uint8_t* B, const uint8_t* SA,
+                               const uint8_t* SB, int af, int bf, int blocks) {
+    DevBuf dA = upload(A, 2048), dB = upload(B, 2048), dSA = upload(SA, 64),
+           dSB = upload(SB, 64);
+    return launch_fetch((size_t)blocks * 256, [&](float* dD) {
+        hipLaunchKernelGGL(mx_kernel(af, bf), dim3(blocks), dim3(WAVE), 0, 0,
+                           dA.as<const uint8_t>(), dB.as<const uint8_t>(),
+                           dSA.as<const uint8_t>(), dSB.as<const uint8_t>(), dD);
+    });
+}
+
+py::bytes mfma_fp8_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
+                            const std::string& a_fmt, const std::string& b_fmt,
+                            int blocks) {
+    require_dev(dev);
+    require_tile_blocks(blocks);
+    int af = parse_fmt(a_fmt, {FMT_E4M3, FMT_E5M2}, "a_fmt must be 'e4m3' or 'e5m2'");
+    int bf = parse_fmt(b_fmt, {FMT_E4M3, FMT_E5M2}, "b_fmt must be 'e4m3' or 'e5m2'");
+    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
+    const uint8_t* pa = code_buffer(ia, 512, "A_codes must be 16x32 contiguous uint8");
+    const uint8_t* pb = code_buffer(ib, 512, "B_codes must be 32x16 contiguous uint8");
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_fp8_tile(pa, pb, af, bf, blocks));
+}
+
+py::bytes mfma_mx_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
+                           py::buffer A_scales, py::buffer B_scales,
+                           const std::string& a_fmt, const std::string& b_fmt,
+                           int blocks) {
+    require_dev(dev);
+    require_tile_blocks(blocks);
+    int af = parse_fmt(a_fmt, {FMT_E4M3, FMT_E5M2, FMT_E2M1},
+                       "a_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
+    int bf = parse_fmt(b_fmt, {FMT_E4M3, FMT_E5M2, FMT_E2M1},
+                       "b_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
+    py::buffer_info ia = A_codes.request(), ib = B_codes.request();
+    py::buffer_info isa = A_scales.request(), isb = B_scales.request();
+    const uint8_t* pa = code_buffer(ia, 2048, "A_codes must be 16x128 contiguous uint8");
+    const uint8_t* pb = code_buffer(ib, 2048, "B_codes must be 128x16 contiguous uint8");
+    const uint8_t* psa = code_buffer(isa, 64, "A_scales must be 16x4 contiguous uint8");
+    const uint8_t* psb = code_buffer(isb, 64, "B_scales must be 4x16 contiguous uint8");
+    for (int i = 0; i < 2048; i++) {
+        require(af != FMT_E2M1 || pa[i] < 16, "A_codes: an e2m1 code must be below 16");
+        require(bf != FMT_E2M1 || pb[i] < 16, "B_codes: an e2m1 code must be below 16");
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    return as_bytes(run_mx_tile(pa, pb, psa, psb, af, bf, blocks));
+}
+
+void launch_mx_burn(int fmt, int blocks, float* out, int iters) {
+    if (fmt == FMT_E2M1)
+        hipLaunchKernelGGL(mfma_mx_burn<FMT_E2M1>, dim3(blocks), dim3(256), 0, 0, out, iters);
+    else
+        hipLaunchKernelGGL(mfma_mx_burn<FMT_E4M3>, dim3(blocks), dim3(256), 0, 0, out, iters);
+}
+
+// launch_mx_burn of one format, in the burns' launcher shape.
+auto mx_burn_launcher(int fmt) {
+    return [fmt](int blocks, float* out, int iters) { launch_mx_burn(fmt, blocks, out, iters); };
+}
+
+py::dict mfma_mx_burn_run(int dev, const std::string& fmt, int iters, int blocks) {
+    require_dev(dev);
+    int f = parse_fmt(fmt, {FMT_E4M3, FMT_E2M1}, "fmt must be 'e4m3' or 'e2m1'");
+    require(iters > 0, "iters must be > 0");
+    require_burn_blocks(blocks);
+    HIP_CHECK(hipSetDevice(dev));
+    return raw_burn(mx_burn_launcher(f), burn_blocks(dev, blocks, 2), iters);
+}
+
+struct LowpTile {
+    bool ok;
+    uint64_t bad_slabs;
+};
+
+// The exact tile of lowp_exact_operands on `blocks` blocks: slab 0 against the
+// host, every other slab against slab 0.
 LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
     LowpOperands op = lowp_exact_operands(fmt, mx, seed);
     std::vector<float> hD = mx
         ? run_mx_tile(op.A.data(), op.B.data(), op.SA.data(), op.SB.data(), fmt, fmt, blocks)
         : run_fp8_tile(op.A.data(), op.B.data(), fmt, fmt, blocks);
     return {std::memcmp(hD.data(), op.ref.data(), 256 * 4) == 0, slab_mismatches(hD, 256)};
-}
-
-struct LowpBurn {
-    double tflops;
-    float ms;
-    uint64_t mismatches;
-};
-
-LowpBurn lowp_timed_burn(int dev, int fmt, int iters) {
-    int grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
-    std::vector<float> h((size_t)grid * 256);
-    DevBuf out_buf(h.size() * 4);
-    float* out = out_buf.as<float>();
-    launch_mx_burn(fmt, grid, out, 64);
-    HIP_CHECK(hipDeviceSynchronize());
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0));
-    launch_mx_burn(fmt, grid, out, iters);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost));
-    // FLOPs: blocks × 4 waves/WG × accumulators × iters × 2·16·16·128
-    double flops = (double)grid * 4.0 * MX_BURN_ACCS * iters * 2.0 * 16 * 16 * 128;
-    return {flops / (ms * 1e9), ms, burn_mismatches(h)};
 }
 
 // FP8 / MX-FP8 / MX-FP4 matrix-core probe: one fixed exact tile per form on
@@ -1513,15 +1499,18 @@ LowpBurn lowp_timed_burn(int dev, int fmt, int iters) {
 // (16x16x128; the 32x32x64 form moves half the operand bytes per FLOP).
 // FP6 operands are not probed: same datapath and rate as FP4.
 py::dict mfma_probe_lowp(int dev, int burn_iters) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     require(burn_iters > 0, "burn_iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
     LowpTile fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, LOWP_SEED_FP8);
     LowpTile mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, LOWP_SEED_MX_FP8);
     LowpTile mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, LOWP_SEED_MX_FP4);
-    LowpBurn b8 = lowp_timed_burn(dev, FMT_E4M3, burn_iters);
-    LowpBurn b4 = lowp_timed_burn(dev, FMT_E2M1, burn_iters);
+    int burn_grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
+    // FLOPs per block and iteration: 4 waves/WG × accumulators × 2·16·16·128
+    const double burn_flops = 4.0 * MX_BURN_ACCS * 2.0 * 16 * 16 * 128;
+    TimedBurn b8 = timed_burn(mx_burn_launcher(FMT_E4M3), burn_grid, burn_iters, burn_flops);
+    TimedBurn b4 = timed_burn(mx_burn_launcher(FMT_E2M1), burn_grid, burn_iters, burn_flops);
     py::dict d;
     d["fp8_ok"] = fp8.ok;
     d["mx_fp8_ok"] = mx8.ok;
@@ -1553,6 +1542,10 @@ constexpr int SWEEP_THREADS = 256;
 constexpr int SWEEP_DEFAULT_REPS = 2;
 constexpr int SWEEP_MAX_LAUNCHES = 3;
 constexpr size_t SWEEP_LDS_GRANULE = 4096;   // a multiple of 4 × the largest block
+
+void require_sweep_reps(int reps) {
+    require(reps >= 1 && reps <= SWEEP_MAX_REPS, "reps must be in 1..2^20");
+}
 
 int sweep_kind(const std::string& s, const char* what) {
     for (int k = 0; k < SK_COUNT; k++)
@@ -1600,14 +1593,6 @@ void sweep_parse_poison(const py::object& poison, uint32_t kinds, SweepParams& p
     p.poison_simd = (uint32_t)simd;
     p.poison_xor = (uint32_t)bits;
 }
-
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() { HIP_CHECK(hipEventCreate(&e)); }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    Event(const Event&) = delete;
-    Event& operator=(const Event&) = delete;
-};
 
 // Inputs and golden tiles of the selected kinds. f32, fp8, MX-fp8 and MX-fp4
 // are the host references of mfma_probe_f32 and mfma_probe_lowp; bf16 has no
@@ -1706,10 +1691,8 @@ SweepLaunch sweep_launch(int dev, const SweepSetup& setup, SweepParams p, int bl
     }
     if (!exclusive) lds = std::min(lds, fallback);
 
-    DevBuf d_in(sizeof(SweepInputs));
-    HIP_CHECK(hipMemcpy(d_in.p, &setup.in, sizeof(SweepInputs), hipMemcpyHostToDevice));
+    DevBuf d_in = upload(&setup.in, sizeof(SweepInputs));
     const int cus = compute_units(dev);
-    Event t0, t1;
     SweepLaunch out;
     for (;;) {
         int blocks = blocks_arg > 0 ? blocks_arg
@@ -1720,10 +1703,12 @@ SweepLaunch sweep_launch(int dev, const SweepSetup& setup, SweepParams p, int bl
         // an unwritten record reads as all ones: no valid XCD, every counter bad
         HIP_CHECK(hipMemset(d_rec.p, 0xff, n_words * 4));
         p.lds_words = (uint32_t)(lds / 4);
-        HIP_CHECK(hipEventRecord(t0.e));
-        hipLaunchKernelGGL(unit_sweep, dim3(blocks), dim3(threads), lds, 0,
-                           d_in.as<const SweepInputs>(), p, d_rec.as<uint32_t>());
-        hipError_t launched = hipGetLastError();
+        hipError_t launched = hipSuccess;
+        out.ms = timed_ms([&] {
+            hipLaunchKernelGGL(unit_sweep, dim3(blocks), dim3(threads), lds, 0,
+                               d_in.as<const SweepInputs>(), p, d_rec.as<uint32_t>());
+            launched = hipGetLastError();
+        });
         if (launched != hipSuccess && exclusive) {
             // the large-LDS launch was refused before anything ran
             lds = fallback;
@@ -1731,9 +1716,6 @@ SweepLaunch sweep_launch(int dev, const SweepSetup& setup, SweepParams p, int bl
             continue;
         }
         HIP_CHECK(launched);
-        HIP_CHECK(hipEventRecord(t1.e));
-        HIP_CHECK(hipEventSynchronize(t1.e));
-        HIP_CHECK(hipEventElapsedTime(&out.ms, t0.e, t1.e));
         HIP_CHECK(hipDeviceSynchronize());
         out.records.resize(n_words);
         HIP_CHECK(hipMemcpy(out.records.data(), d_rec.p, n_words * 4, hipMemcpyDeviceToHost));
@@ -1755,9 +1737,9 @@ py::dict sweep_golden_dict(uint32_t kinds, const SweepSetup& setup) {
 // Raw entry point: one launch, no retries.
 py::dict unit_sweep_run(int dev, const std::vector<std::string>& kinds, int reps, int blocks,
                         const py::object& poison, int threads) {
-    require(dev >= 0, "dev must be >= 0");
+    require_dev(dev);
     uint32_t mask = sweep_kind_mask(kinds);
-    require(reps >= 1 && reps <= SWEEP_MAX_REPS, "reps must be in 1..2^20");
+    require_sweep_reps(reps);
     require(blocks >= 0 && blocks <= SWEEP_MAX_BLOCKS, "blocks must be in 0..4096");
     require(threads == 256 || threads == 512 || threads == 1024,
             "threads must be 256, 512 or 1024");
@@ -1796,8 +1778,8 @@ size_t sweep_simds_seen(const std::vector<uint32_t>& records) {
 // only while the merged records do not cover 4 SIMDs on every CU. A HIP error
 // propagates; nothing is relaunched after one.
 py::dict unit_sweep_probe(int dev, bool low_precision, int reps) {
-    require(dev >= 0, "dev must be >= 0");
-    require(reps >= 1 && reps <= SWEEP_MAX_REPS, "reps must be in 1..2^20");
+    require_dev(dev);
+    require_sweep_reps(reps);
     uint32_t mask = 1u << SK_F32 | 1u << SK_BF16 | 1u << SK_LDS;
     if (low_precision) mask |= 1u << SK_FP8 | 1u << SK_MX_FP8 | 1u << SK_MX_FP4;
     HIP_CHECK(hipSetDevice(dev));
