@@ -35,6 +35,12 @@ PCIE_GBPS_FLOOR = 20.0  # Gen5 x16 is ~63 GB/s; below 20 = degraded link
 # (4320 and 8237 TF).
 MX_FP8_TFLOPS_FLOOR_MI355X = 2000.0
 MX_FP4_TFLOPS_FLOOR_MI355X = 4000.0
+# FP64 and INT8 burns (profiles/mfma_formats.md), by the same rule. No FP64
+# matrix peak is on record here, so that floor is 0.5× the measured median
+# (76.3 TF) alone; INT8 is 2× bf16 per clock (~5000 TOPS): the smaller of
+# 0.4 × 5000 and 0.5 × the measured median (4487 TOPS).
+F64_TFLOPS_FLOOR_MI355X = 38.0
+I8_TOPS_FLOOR_MI355X = 2000.0
 
 
 def _ext():
@@ -46,6 +52,19 @@ def _ext():
             "not built; run `python -c 'from setup import build_hip; build_hip()'`"
         ) from e
     return _gpuprobe
+
+
+def _ext_formats():
+    """The FP64 / FP16 / INT8 / 2:4-sparse extension; loaded only for
+    probe_device(matrix_formats=True)."""
+    try:
+        from .. import _gpuprobe_formats
+    except ImportError as e:
+        raise RuntimeError(
+            "kata_xpu_device_plugin_amd._gpuprobe_formats (HIP/gfx950) extension "
+            "is not built; run `python -c 'from setup import build_hip; build_hip()'`"
+        ) from e
+    return _gpuprobe_formats
 
 
 @dataclass
@@ -82,6 +101,20 @@ class ProbeReport:
     mfma_mx_fp4_slab_mismatches: int = -1
     mx_fp8_burn_mismatches: int = -1
     mx_fp4_burn_mismatches: int = -1
+    # FP64 / FP16 / INT8 / 2:4-sparse matrix-core probes
+    # (probe_device(matrix_formats=True))
+    mfma_f64_ok: bool = False
+    mfma_f16_ok: bool = False
+    mfma_i8_ok: bool = False
+    mfma_sparse_f16_ok: bool = False
+    mfma_f64_slab_mismatches: int = -1
+    mfma_f16_slab_mismatches: int = -1
+    mfma_i8_slab_mismatches: int = -1
+    mfma_sparse_f16_slab_mismatches: int = -1
+    f64_tflops: float = 0.0
+    i8_tops: float = 0.0
+    f64_burn_mismatches: int = -1
+    i8_burn_mismatches: int = -1
     # placement-recording unit sweep (probe_device(unit_sweep=True))
     unit_sweep_ran: bool = False
     sweep_cus_seen: int = -1
@@ -109,6 +142,9 @@ def probe_device(
     fp8_tflops_floor: Optional[float] = None,
     fp4_tflops_floor: Optional[float] = None,
     unit_sweep: bool = False,
+    matrix_formats: bool = False,
+    f64_tflops_floor: Optional[float] = None,
+    i8_tops_floor: Optional[float] = None,
 ) -> ProbeReport:
     """Run the full probe suite on one GPU; raises only on infrastructure
     errors — a sick GPU yields passed=False with reasons.
@@ -118,7 +154,10 @@ def probe_device(
 
     `unit_sweep=True` adds the placement-recording sweep: the exact tiles
     through every SIMD of every CU, failures named by XCD / SE / CU / SIMD,
-    and incomplete coverage reported as a failure."""
+    and incomplete coverage reported as a failure.
+
+    `matrix_formats=True` adds the FP64, FP16, INT8 and 2:4-sparse
+    matrix-core probes of the _gpuprobe_formats extension (gfx950 only)."""
     g = _ext()
     rep = ProbeReport(device=dev)
     info = g.device_info(dev)
@@ -214,6 +253,10 @@ def probe_device(
     if unit_sweep:
         _probe_unit_sweep(g, rep, dev, low_precision and is_mi355x)
 
+    if matrix_formats:
+        _probe_matrix_formats(rep, dev, burn_iters, is_mi355x,
+                              f64_tflops_floor, i8_tops_floor)
+
     mt = g.memtest(dev, memtest_bytes)
     rep.memtest_mismatches = int(mt["mismatches"])
     if rep.memtest_mismatches:
@@ -267,6 +310,48 @@ def _probe_low_precision(g, rep: ProbeReport, dev: int, burn_iters: int,
         if tflops < floor:
             rep.failures.append(
                 f"{label} MFMA {tflops:.0f} TFLOP/s < floor {floor:.0f}")
+
+
+def _probe_matrix_formats(rep: ProbeReport, dev: int, burn_iters: int,
+                          is_mi355x: bool, f64_tflops_floor: Optional[float],
+                          i8_tops_floor: Optional[float]) -> None:
+    """FP64 / FP16 / INT8 / 2:4-sparse tiles and the FP64 and INT8 burns; one
+    failure per failed check. The extension is loaded only here."""
+    if not is_mi355x:
+        # the kernels are built for gfx950; the K=64 i8 and sparse forms and
+        # the 32x32x16 f16 form do not exist elsewhere
+        rep.failures.append(
+            f"matrix-format MFMA probes skipped: {rep.gcn_arch or 'unknown arch'} "
+            "is not gfx950")
+        return
+    if f64_tflops_floor is None:
+        f64_tflops_floor = F64_TFLOPS_FLOOR_MI355X
+    if i8_tops_floor is None:
+        i8_tops_floor = I8_TOPS_FLOOR_MI355X
+    mf = _ext_formats().mfma_probe_formats(dev, burn_iters)
+    for label, key in (("f64", "f64"), ("f16", "f16"), ("i8", "i8"),
+                       ("2:4-sparse f16", "sparse_f16")):
+        ok = bool(mf[f"{key}_ok"])
+        slabs = int(mf[f"{key}_slab_mismatches"])
+        setattr(rep, f"mfma_{key}_ok", ok)
+        setattr(rep, f"mfma_{key}_slab_mismatches", slabs)
+        if not ok:
+            rep.failures.append(
+                f"{label} MFMA mismatch (exact tile differs from the host product)")
+        if slabs:
+            rep.failures.append(f"{label} MFMA: {slabs} blocks differ from block 0")
+    for label, key, rate, unit, floor in (
+            ("f64", "f64", "f64_tflops", "TFLOP/s", f64_tflops_floor),
+            ("i8", "i8", "i8_tops", "TOP/s", i8_tops_floor)):
+        value = float(mf[rate])
+        burn = int(mf[f"{key}_burn_mismatches"])
+        setattr(rep, rate, value)
+        setattr(rep, f"{key}_burn_mismatches", burn)
+        if burn:
+            rep.failures.append(f"{label} MFMA burn: {burn} lanes differ from wave 0")
+        if value < floor:
+            rep.failures.append(
+                f"{label} MFMA {value:.0f} {unit} < floor {floor:.0f}")
 
 
 def _probe_unit_sweep(g, rep: ProbeReport, dev: int, low_precision: bool) -> None:

@@ -1,7 +1,7 @@
 """GPU burn-in CLI: validate every visible GPU before vfio binding.
 
     python -m kata_xpu_device_plugin_amd.tools.burnin [--json] [--quick] [--low-precision]
-                                                      [--unit-sweep]
+                                                      [--unit-sweep] [--matrix-formats]
 
 Exit code 0 iff every GPU passes. See health/gpuprobe.py for the probes.
 """
@@ -26,6 +26,9 @@ def main(argv=None) -> int:
     p.add_argument("--unit-sweep", action="store_true",
                    help="also run the exact tiles through every SIMD of every "
                         "CU and name a failing unit by XCD / SE / CU / SIMD")
+    p.add_argument("--matrix-formats", action="store_true",
+                   help="also probe the FP64, FP16, INT8 and 2:4-sparse "
+                        "matrix-core paths (gfx950 only)")
     p.add_argument("--bandwidth-gib", type=float, default=2.0)
     p.add_argument("--memtest-gib", type=float, default=2.0)
     p.add_argument("--parallel", action="store_true",
@@ -48,6 +51,8 @@ def main(argv=None) -> int:
         kw["low_precision"] = True
     if args.unit_sweep:
         kw["unit_sweep"] = True
+    if args.matrix_formats:
+        kw["matrix_formats"] = True
     if args.soak_minutes > 0:
         import time
         deadline = time.monotonic() + args.soak_minutes * 60

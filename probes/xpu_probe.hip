@@ -60,19 +60,11 @@
 #include <string>
 #include <vector>
 
+#include "probe_host.h"
+
 namespace py = pybind11;
 
-#define HIP_CHECK(expr)                                                       \
-    do {                                                                      \
-        hipError_t _e = (expr);                                               \
-        if (_e != hipSuccess)                                                 \
-            throw std::runtime_error(std::string(#expr) + " failed: " +       \
-                                     hipGetErrorString(_e));                  \
-    } while (0)
-
 namespace {
-
-constexpr int WAVE = 64;
 
 // ---------------------------------------------------------------------------
 // HBM bandwidth: grid-stride float4 copy. 256 threads/WG, ≥2048 WGs so all
@@ -632,28 +624,10 @@ unit_sweep(const SweepInputs* __restrict__ in, SweepParams p, uint32_t* __restri
 }
 
 // ---------------------------------------------------------------------------
-// Host-side wrappers
+// Host-side wrappers. The argument checks (run before the first HIP call of
+// every entry point), the RAII handles and the launch, fetch, timing and
+// comparison helpers are in probe_host.h, shared with xpu_probe_formats.hip.
 // ---------------------------------------------------------------------------
-
-// Argument checks run before the first HIP call of every entry point, so a
-// bad argument is a ValueError on any machine, with or without a GPU.
-void require(bool cond, const char* what) {
-    if (!cond) throw std::invalid_argument(what);
-}
-
-void require_dev(int dev) { require(dev >= 0, "dev must be >= 0"); }
-
-constexpr int MAX_TILE_BLOCKS = 4096;   // 16 MiB of bf16-tile slabs at most
-constexpr int MAX_BURN_BLOCKS = 65536;  // 64 MiB of burn output at most
-
-void require_tile_blocks(int blocks) {
-    require(blocks >= 1 && blocks <= MAX_TILE_BLOCKS, "blocks out of range");
-}
-
-// 0 asks for the entry point's own per-CU default (burn_blocks).
-void require_burn_blocks(int blocks) {
-    require(blocks >= 0 && blocks <= MAX_BURN_BLOCKS, "blocks out of range");
-}
 
 // "e4m3" / "e5m2" / "e2m1" → the instruction's format number, if the entry
 // point allows that format.
@@ -661,110 +635,6 @@ int parse_fmt(const std::string& s, std::initializer_list<int> allowed, const ch
     int f = s == "e4m3" ? FMT_E4M3 : s == "e5m2" ? FMT_E5M2 : s == "e2m1" ? FMT_E2M1 : -1;
     require(std::find(allowed.begin(), allowed.end(), f) != allowed.end(), what);
     return f;
-}
-
-// Device memory, pinned host memory and events that are released on every
-// path, exceptions included.
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct HostBuf {
-    void* p = nullptr;
-    explicit HostBuf(size_t bytes) { HIP_CHECK(hipHostMalloc(&p, bytes)); }
-    ~HostBuf() { if (p) (void)hipHostFree(p); }
-    HostBuf(const HostBuf&) = delete;
-    HostBuf& operator=(const HostBuf&) = delete;
-};
-
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() { HIP_CHECK(hipEventCreate(&e)); }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    Event(const Event&) = delete;
-    Event& operator=(const Event&) = delete;
-};
-
-// A device copy of `bytes` bytes at `src`.
-DevBuf upload(const void* src, size_t bytes) {
-    DevBuf d(bytes);
-    HIP_CHECK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    return d;
-}
-
-// Milliseconds the device spent on what `enqueue` puts on the null stream:
-// one kernel launch or one async copy, and nothing else. A refused launch is
-// reported once the closing event is recorded, outside the timed window.
-template <class F>
-float timed_ms(F&& enqueue) {
-    Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e));
-    enqueue();
-    HIP_CHECK(hipEventRecord(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-    return ms;
-}
-
-template <class F>
-float best_timed_ms(int iters, F&& enqueue) {
-    float best = 1e30f;
-    for (int i = 0; i < iters; i++) best = std::min(best, timed_ms(enqueue));
-    return best;
-}
-
-// `launch(out)` starts one kernel that writes `n` floats at `out`; they come
-// back once it has run.
-template <class F>
-std::vector<float> launch_fetch(size_t n, F&& launch) {
-    DevBuf out(n * 4);
-    launch(out.as<float>());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    std::vector<float> h(n);
-    HIP_CHECK(hipMemcpy(h.data(), out.p, n * 4, hipMemcpyDeviceToHost));
-    return h;
-}
-
-int compute_units(int dev) {
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    return prop.multiProcessorCount;
-}
-
-// A C-contiguous buffer of exactly `count` items of `itemsize` bytes.
-const void* tile_buffer(const py::buffer_info& info, size_t itemsize,
-                        size_t count, const char* what) {
-    bool ok = (size_t)info.itemsize == itemsize && (size_t)info.size == count;
-    py::ssize_t stride = info.itemsize;
-    for (py::ssize_t d = info.ndim - 1; ok && d >= 0; d--) {
-        if (info.shape[d] != 1 && info.strides[d] != stride) ok = false;
-        stride *= info.shape[d];
-    }
-    require(ok, what);
-    return info.ptr;
-}
-
-template <class T>
-py::bytes as_bytes(const std::vector<T>& v) {
-    return py::bytes(reinterpret_cast<const char*>(v.data()), v.size() * sizeof(T));
-}
-
-// Slabs of `slab` floats whose bits differ from slab 0. Every block of a
-// tile launch computes the same thing, so a non-zero count is a sick CU.
-uint64_t slab_mismatches(const std::vector<float>& d, size_t slab) {
-    uint64_t bad = 0;
-    for (size_t s = 1; s * slab < d.size(); s++)
-        if (std::memcmp(d.data() + s * slab, d.data(), slab * sizeof(float)) != 0) bad++;
-    return bad;
 }
 
 int device_count() {
@@ -881,10 +751,6 @@ uint64_t lds_mismatches(const std::vector<float>& out, int iters) {
     for (size_t i = 0; i < out.size(); i++)
         if (out[i] != (float)iters * (float)(8 * (int)(i & 255) + 7168)) bad++;
     return bad;
-}
-
-int burn_blocks(int dev, int blocks, int per_cu) {
-    return blocks > 0 ? blocks : compute_units(dev) * per_cu;
 }
 
 void launch_lds_burn(int blocks, float* out, int iters) {
@@ -1240,53 +1106,6 @@ py::bytes mfma_bf16_tile_run(int dev, py::buffer A_bits, py::buffer B_bits, int 
         ib, 2, 512, "B_bits must be 16x32 contiguous uint16");
     HIP_CHECK(hipSetDevice(dev));
     return as_bytes(run_bf16_tile(pa, pb, blocks));
-}
-
-// Output elements whose bits differ from lane (i & 63) of block 0's wave 0.
-// Every wave of the burn computes the same 64 values.
-uint64_t burn_mismatches(const std::vector<float>& out) {
-    uint64_t bad = 0;
-    for (size_t i = WAVE; i < out.size(); i++)
-        if (std::memcmp(&out[i], &out[i & (WAVE - 1)], 4) != 0) bad++;
-    return bad;
-}
-
-// The burns share a launcher shape, launch(blocks, out, iters): `blocks`
-// 256-thread workgroups that write blocks × 256 floats at `out`.
-
-// What the raw burn entry points return: one launch, no warm-up.
-template <class F>
-py::dict raw_burn(F&& launch, int blocks, int iters) {
-    std::vector<float> h = launch_fetch((size_t)blocks * 256, [&](float* out) {
-        launch(blocks, out, iters);
-    });
-    py::dict d;
-    d["lanes"] = py::bytes(reinterpret_cast<const char*>(h.data()), WAVE * 4);
-    d["mismatches"] = burn_mismatches(h);
-    d["blocks"] = blocks;
-    return d;
-}
-
-struct TimedBurn {
-    double tflops;
-    float ms;
-    uint64_t mismatches;
-};
-
-// What the probes run: a warm-up launch of 64 iterations, one timed launch of
-// `iters` on the same buffer, and the check that all its waves agree bit for
-// bit. `flops` is per block and iteration.
-template <class F>
-TimedBurn timed_burn(F&& launch, int blocks, int iters, double flops) {
-    std::vector<float> h((size_t)blocks * 256);
-    DevBuf out_buf(h.size() * 4);
-    float* out = out_buf.as<float>();
-    launch(blocks, out, 64);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    float ms = timed_ms([&] { launch(blocks, out, iters); });
-    HIP_CHECK(hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost));
-    return {(double)blocks * flops * iters / (ms * 1e9), ms, burn_mismatches(h)};
 }
 
 void launch_bf16_burn(int blocks, float* out, int iters) {

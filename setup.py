@@ -2,8 +2,9 @@
 
 * ``kata_xpu_device_plugin_amd._native`` — C++ fast paths (g++; runs on any
   Linux node, no GPU/ROCm needed).
-* ``kata_xpu_device_plugin_amd._gpuprobe`` — HIP gfx950 health probes,
-  compiled by hipcc (cross-compiles fine on GPU-less builders). Built by
+* ``kata_xpu_device_plugin_amd._gpuprobe`` and ``._gpuprobe_formats`` — HIP
+  gfx950 health probes (the second: FP64 / FP16 / INT8 / 2:4-sparse matrix
+  cores), compiled by hipcc (cross-compiles fine on GPU-less builders). Built by
   ``build_hip()`` below / __graft_entry__.build(), not by setuptools, so a
   missing ROCm toolchain never breaks the control-plane build.
 
@@ -19,28 +20,43 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = "kata_xpu_device_plugin_amd"
 
 
+# HIP extension module → its source under probes/. Both include
+# probes/probe_host.h.
+HIP_EXTENSIONS = {
+    "_gpuprobe": "xpu_probe.hip",
+    "_gpuprobe_formats": "xpu_probe_formats.hip",
+}
+
+
 def build_hip(arch: str = "gfx950", verbose: bool = True) -> str:
-    """Compile probes/xpu_probe.hip → kata_xpu_device_plugin_amd/_gpuprobe.so."""
+    """Compile probes/xpu_probe.hip → kata_xpu_device_plugin_amd/_gpuprobe.so
+    and probes/xpu_probe_formats.hip → …/_gpuprobe_formats.so with the same
+    flags; returns the _gpuprobe path. An output newer than its source and
+    the shared header is kept."""
     import sysconfig
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = os.path.join(ROOT, "probes", "xpu_probe.hip")
+    header = os.path.join(ROOT, "probes", "probe_host.h")
     ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
-    out = os.path.join(ROOT, PKG, f"_gpuprobe{ext}")
-    if os.path.exists(out) and os.path.getmtime(out) > os.path.getmtime(src):
-        return out
-    cmd = [
-        hipcc, f"--offload-arch={arch}", "-O3", "-std=c++17",
-        "-fPIC", "-shared",
-        "-x", "hip", src,
-        f"-I{pybind11.get_include()}",
-        f"-I{sysconfig.get_paths()['include']}",
-        "-o", out,
-    ]
-    if verbose:
-        print("+", " ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    return out
+    outs = {}
+    for mod, name in HIP_EXTENSIONS.items():
+        src = os.path.join(ROOT, "probes", name)
+        out = outs[mod] = os.path.join(ROOT, PKG, f"{mod}{ext}")
+        newest = max(os.path.getmtime(src), os.path.getmtime(header))
+        if os.path.exists(out) and os.path.getmtime(out) > newest:
+            continue
+        cmd = [
+            hipcc, f"--offload-arch={arch}", "-O3", "-std=c++17",
+            "-fPIC", "-shared",
+            "-x", "hip", src,
+            f"-I{pybind11.get_include()}",
+            f"-I{sysconfig.get_paths()['include']}",
+            "-o", out,
+        ]
+        if verbose:
+            print("+", " ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+    return outs["_gpuprobe"]
 
 
 if __name__ == "__main__" or "setuptools" in sys.modules:
