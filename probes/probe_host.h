@@ -1,8 +1,9 @@
 // Host-side helpers shared by the probe extensions (xpu_probe.hip →
 // _gpuprobe, xpu_probe_formats.hip → _gpuprobe_formats): argument checks,
-// RAII device/host/event handles, the one launch, fetch and timing path, and
-// the slab / burn comparisons. Everything has internal linkage; each extension
-// is one translation unit.
+// RAII device/host/event handles, the one launch, fetch and timing path, the
+// slab / tile / burn comparisons and the tiles' bit generator. Everything has
+// internal linkage; each extension is one translation unit. The device side
+// both share is mfma_forms.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -139,6 +140,14 @@ inline const void* tile_buffer(const py::buffer_info& info, size_t itemsize,
     return info.ptr;
 }
 
+// A C-contiguous buffer of exactly `count` items of type T (by format code,
+// so an int8 view is not taken for uint8 nor f32 for i32).
+template <class T>
+const T* typed_buffer(const py::buffer_info& info, size_t count, const char* what) {
+    require(info.format == py::format_descriptor<T>::format(), what);
+    return (const T*)tile_buffer(info, sizeof(T), count, what);
+}
+
 template <class T>
 py::bytes as_bytes(const std::vector<T>& v) {
     return py::bytes(reinterpret_cast<const char*>(v.data()), v.size() * sizeof(T));
@@ -151,6 +160,25 @@ inline uint64_t slab_mismatches(const std::vector<float>& d, size_t slab) {
     for (size_t s = 1; s * slab < d.size(); s++)
         if (std::memcmp(d.data() + s * slab, d.data(), slab * sizeof(float)) != 0) bad++;
     return bad;
+}
+
+struct TileVerdict {
+    bool ok;
+    uint64_t bad_slabs;
+};
+
+// Slab 0 of `words` against the host's `ref`, every other slab against slab 0.
+template <class T>
+TileVerdict judge_tile(const std::vector<float>& words, const std::vector<T>& ref) {
+    size_t slab = ref.size() * sizeof(T) / 4;
+    return {std::memcmp(words.data(), ref.data(), slab * 4) == 0,
+            slab_mismatches(words, slab)};
+}
+
+// The generator behind the probes' fixed tiles: 31 fresh bits per call.
+inline uint32_t lcg_bits(uint64_t& s) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(s >> 33);
 }
 
 inline int burn_blocks(int dev, int blocks, int per_cu) {

@@ -44,6 +44,9 @@
 //   * *_run / hbm_copy_check : raw entry points that return what a kernel
 //     computed, for tests against independent references.
 //
+// The matrix-core lane maps are stated once, in mfma_forms.h; the tile kernels
+// and the unit sweep both run on those forms.
+//
 // Wavefront size is 64 everywhere (gfx950; cdna_hip_programming.md §1).
 // Build: hipcc --offload-arch=gfx950 (driven by setup.py / __graft_entry__).
 
@@ -60,6 +63,7 @@
 #include <string>
 #include <vector>
 
+#include "mfma_forms.h"
 #include "probe_host.h"
 
 namespace py = pybind11;
@@ -162,68 +166,36 @@ __global__ void pointer_chase(const uint32_t* __restrict__ next,
 }
 
 // ---------------------------------------------------------------------------
-// f32-input MFMA correctness tile: D = A·B for one 16×16×4 step per wave.
-// Lane mapping from cdna_hip_programming.md §3 (documented, exact f32):
-//   a = A[l&15][l>>4]   (K=4: k = l>>4)
-//   b = B[l>>4][l&15]
-//   D reg j ↔ D[(l>>4)*4 + j][l&15]
+// Matrix-core tile kernels: one wave per block, every block the same tile into
+// its own slab (form_tile). The lane maps are in mfma_forms.h.
 // ---------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Every block computes the same tile and stores its own 16×16 slab at
-// D + blockIdx.x*256, so a launch of 2×CUs blocks puts the tile through the
-// matrix cores of every CU and the host can compare the slabs.
 __global__ void mfma_f32_tile(const float* __restrict__ A,  // 16×4 row-major
                               const float* __restrict__ B,  // 4×16 row-major
                               const float* __restrict__ C,  // 16×16 or nullptr (= 0)
                               float* __restrict__ D) {      // gridDim.x × 16×16
-    int l = threadIdx.x & (WAVE - 1);
-    int row = l & 15, k = l >> 4;
-    float a = A[row * 4 + k];
-    float b = B[k * 16 + (l & 15)];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (C) {
-        for (int j = 0; j < 4; j++) acc[j] = C[((l >> 4) * 4 + j) * 16 + (l & 15)];
-    }
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-    if (threadIdx.x < WAVE) {
-        float* slab = D + (size_t)blockIdx.x * 256;
-        for (int j = 0; j < 4; j++) slab[((l >> 4) * 4 + j) * 16 + (l & 15)] = acc[j];
-    }
+    form_tile<MfmaF32x16x16x4>({A, B}, C, D);
 }
-
-// ---------------------------------------------------------------------------
-// bf16 MFMA: one verified 32×32×16 tile + a throughput burn loop.
-// v_mfma_f32_32x32x16_bf16: each lane holds 8 bf16 of A and B (4 VGPRs),
-// 16 f32 accumulators. C/D mapping (cdna_hip_programming.md §3):
-//   col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5)
-// A/B input mapping (K=16, 2 lane-halves of 32): lane l holds
-//   A[l&31][(l>>5)*8 + j]  and  B[(l>>5)*8 + j][l&31],  j = 0..7.
-// The numeric check against a host reference catches any mapping error.
-// ---------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ void mfma_bf16_tile(const __bf16* __restrict__ A,  // 32×16 row-major
                                const __bf16* __restrict__ B,  // 16×32 row-major
                                float* __restrict__ D) {       // gridDim.x × 32×32
-    int l = threadIdx.x & (WAVE - 1);
-    int half = l >> 5;          // which 8-wide K slice
-    int lane32 = l & 31;
-    bf16x8 a, b;
-    for (int j = 0; j < 8; j++) {
-        a[j] = A[lane32 * 16 + half * 8 + j];
-        b[j] = B[(half * 8 + j) * 32 + lane32];
-    }
-    f32x16 acc = {};
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-    if (threadIdx.x < WAVE) {
-        float* slab = D + (size_t)blockIdx.x * 1024;  // one slab per block
-        for (int reg = 0; reg < 16; reg++) {
-            int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
-            slab[row * 32 + lane32] = acc[reg];
-        }
-    }
+    form_tile<Mfma32x32x16<__bf16>>({A, B}, nullptr, D);
+}
+
+template <int AF, int BF>
+__global__ void mfma_fp8_tile(const uint8_t* __restrict__ A,  // 16×32 codes
+                              const uint8_t* __restrict__ B,  // 32×16 codes
+                              float* __restrict__ D) {        // gridDim.x × 16×16
+    form_tile<MfmaFp8x16x16x32<AF, BF>>({A, B}, nullptr, D);
+}
+
+template <int AF, int BF>
+__global__ void mfma_mx_tile(const uint8_t* __restrict__ A,   // 16×128 codes
+                             const uint8_t* __restrict__ B,   // 128×16 codes
+                             const uint8_t* __restrict__ SA,  // 16×4 E8M0
+                             const uint8_t* __restrict__ SB,  // 4×16 E8M0
+                             float* __restrict__ D) {         // gridDim.x × 16×16
+    form_tile<MfmaMx16x16x128<AF, BF>>({A, B, SA, SB}, nullptr, D);
 }
 
 // Throughput burn: every wave hammers independent accumulators with
@@ -248,103 +220,6 @@ mfma_bf16_burn(float* __restrict__ out, int iters) {
     for (int r = 0; r < 16; r++) s += acc0[r] + acc1[r] + acc2[r] + acc3[r];
     // one store per lane; never zero, so the compiler cannot DCE the loop
     out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
-}
-
-// ---------------------------------------------------------------------------
-// FP8 and block-scaled MX (FP8/FP4) MFMA. Operands arrive as row-major element
-// codes, one uint8 per element; the kernels do the lane packing, so the lane
-// maps below are the ones tests/test_gpu_lowp_kernels.py pins on hardware
-// (decode sweep, one-k-at-a-time identity, scale map).
-//
-// Format numbers are the instruction's own cbsz (A) / blgp (B) encodings.
-// FP6 (e2m3 = 2, e3m2 = 3) needs 6-bit packing and runs at the FP4 rate on
-// the same datapath; it is out of scope here.
-// ---------------------------------------------------------------------------
-constexpr int FMT_E4M3 = 0, FMT_E5M2 = 1, FMT_E2M1 = 4;
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-// v_mfma_f32_16x16x32_{fp8,bf8}_{fp8,bf8}: lane l holds A[l&15][8(l>>4)+j]
-// and B[8(l>>4)+j][l&15] in byte j of its 64-bit operand; C/D as every other
-// 16×16 form (col = l&15, row = 4(l>>4)+reg).
-template <int AF, int BF>
-__global__ void mfma_fp8_tile(const uint8_t* __restrict__ A,  // 16×32 codes
-                              const uint8_t* __restrict__ B,  // 32×16 codes
-                              float* __restrict__ D) {        // gridDim.x × 16×16
-    int l = threadIdx.x & (WAVE - 1);
-    int rc = l & 15, g = l >> 4;
-    uint64_t a = 0, b = 0;
-    for (int j = 0; j < 8; j++) {
-        a |= (uint64_t)A[rc * 32 + 8 * g + j] << (8 * j);
-        b |= (uint64_t)B[(8 * g + j) * 16 + rc] << (8 * j);
-    }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (AF == FMT_E4M3 && BF == FMT_E4M3)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
-    else if constexpr (AF == FMT_E4M3)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_bf8((long)a, (long)b, acc, 0, 0, 0);
-    else if constexpr (BF == FMT_E4M3)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_fp8((long)a, (long)b, acc, 0, 0, 0);
-    else
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8((long)a, (long)b, acc, 0, 0, 0);
-    float* slab = D + (size_t)blockIdx.x * 256;
-    for (int j = 0; j < 4; j++) slab[(g * 4 + j) * 16 + rc] = acc[j];
-}
-
-// v_mfma_scale_f32_16x16x128_f8f6f4 operand maps, as the tests established
-// them on an MI355X (they differ by format, and from the bf16-style guess):
-//   * lane l works on row (A) or column (B) l&15; g = l>>4.
-//   * fp4: 4 dwords, two elements per byte, the even one in the low nibble;
-//     element e = 0..31 of lane group g is k = 32g + e.
-//   * fp8: 8 dwords, element e in byte e; e = 0..15 is k = 16g + e and
-//     e = 16..31 is k = 64 + 16g + (e-16): a lane holds two 16-wide runs,
-//     64 apart, not one 32-wide block.
-//   * byte 0 of the scale VGPR (op_sel 0) of lane (l&15, g) is the E8M0 scale
-//     of k = 32g .. 32g+31 of that row or column — for fp4 the lane's own
-//     elements, for fp8 elements held by other lanes.
-// With these, D[i][j] = Σ_b 2^(sa[i][b]-127)·2^(sb[b][j]-127)·Σ_{k∈32b..32b+31} a·b
-// for every format pair, mixed ones included.
-template <int FMT>
-__device__ constexpr int mx_k(int g, int e) {
-    return FMT == FMT_E2M1 ? 32 * g + e : 64 * (e >> 4) + 16 * g + (e & 15);
-}
-
-// One lane's 32 element codes, in element order, → its operand registers
-// (fp4 fills the first four dwords; the other four are not read).
-template <int FMT>
-__device__ i32x8 pack_mx(const uint8_t (&code)[32]) {
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int e = 0; e < 32; e++) {
-        if constexpr (FMT == FMT_E2M1) w[e >> 3] |= (code[e] & 15u) << (4 * (e & 7));
-        else w[e >> 2] |= (uint32_t)code[e] << (8 * (e & 3));
-    }
-    i32x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = (int)w[i];
-    return v;
-}
-
-template <int AF, int BF>
-__global__ void mfma_mx_tile(const uint8_t* __restrict__ A,   // 16×128 codes
-                             const uint8_t* __restrict__ B,   // 128×16 codes
-                             const uint8_t* __restrict__ SA,  // 16×4 E8M0
-                             const uint8_t* __restrict__ SB,  // 4×16 E8M0
-                             float* __restrict__ D) {         // gridDim.x × 16×16
-    int l = threadIdx.x & (WAVE - 1);
-    int rc = l & 15, g = l >> 4;
-    uint8_t ca[32], cb[32];
-#pragma unroll
-    for (int e = 0; e < 32; e++) {
-        ca[e] = A[rc * 128 + mx_k<AF>(g, e)];
-        cb[e] = B[mx_k<BF>(g, e) * 16 + rc];
-    }
-    i32x8 a = pack_mx<AF>(ca), b = pack_mx<BF>(cb);
-    int sa = SA[rc * 4 + g], sb = SB[g * 16 + rc];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, AF, BF, 0, sa, 0, sb);
-    float* slab = D + (size_t)blockIdx.x * 256;
-    for (int j = 0; j < 4; j++) slab[(g * 4 + j) * 16 + rc] = acc[j];
 }
 
 // Throughput burn on the instruction the tile tests verified. Element e of
@@ -408,10 +283,11 @@ mfma_mx_burn(float* __restrict__ out, int iters) {
 //
 // Every wave recomputes each selected tile `reps` times from a zero
 // accumulator and compares its registers bit for bit with the golden tile the
-// host supplies (same inputs and lane maps as the tile kernels above). The
-// inputs are loop-invariant and the MFMA builtins are pure, so one operand
-// goes through an empty volatile asm in each repetition: without it the
-// compiler computes the tile once, outside the loop.
+// host supplies, through the forms of mfma_forms.h: the inputs, lane maps and
+// instructions of the tile kernels above. The inputs are loop-invariant and
+// the MFMA builtins are pure, so one operand goes through an empty volatile
+// asm in each repetition: without it the compiler computes the tile once,
+// outside the loop.
 //
 // LDS: the workgroup fills its whole allocation with an address pattern and
 // reads it back mirrored (word i was written by thread i % n and is read by
@@ -482,28 +358,21 @@ __device__ __forceinline__ uint32_t sweep_wave_sum(uint32_t v) {
     return v;
 }
 
-template <int FMT>
-__device__ uint32_t sweep_mx(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B,
-                             const uint8_t* __restrict__ SA, const uint8_t* __restrict__ SB,
-                             const float* __restrict__ G, int l, int reps, uint32_t flip) {
-    int rc = l & 15, g = l >> 4;
-    uint8_t ca[32], cb[32];
+// One form's tile, `reps` times on this wave: the lane's wrong-element count.
+template <class Form>
+__device__ __forceinline__ uint32_t sweep_form(const typename Form::In& in,
+                                               const float* __restrict__ G, int l, int reps,
+                                               uint32_t flip) {
+    typename Form::Frag f = Form::load(in, l);
+    float gold[Form::REGS];
 #pragma unroll
-    for (int e = 0; e < 32; e++) {
-        ca[e] = A[rc * 128 + mx_k<FMT>(g, e)];
-        cb[e] = B[mx_k<FMT>(g, e) * 16 + rc];
-    }
-    i32x8 a = pack_mx<FMT>(ca), b = pack_mx<FMT>(cb);
-    int sa = SA[rc * 4 + g], sb = SB[g * 16 + rc];
-    float gold[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) gold[j] = G[(g * 4 + j) * 16 + rc];
+    for (int reg = 0; reg < Form::REGS; reg++) gold[reg] = G[Form::d_index(l, reg)];
     uint32_t n = 0;
     for (int r = 0; r < reps; r++) {
-        sweep_relive(a);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, FMT, FMT, 0, sa, 0, sb);
-        n += sweep_count_bad<4>(acc, gold, flip);
+        sweep_relive(f.a);
+        typename Form::Acc acc = {};
+        acc = Form::mma(f, acc);
+        n += sweep_count_bad<Form::REGS>(acc, gold, flip);
     }
     return n;
 }
@@ -539,74 +408,23 @@ unit_sweep(const SweepInputs* __restrict__ in, SweepParams p, uint32_t* __restri
         bad[SK_LDS] = sweep_wave_sum(wrong);
     }
 
-    if (p.kinds & (1u << SK_F32)) {
-        int rc = l & 15, k = l >> 4;
-        float a = in->a32[rc * 4 + k], b = in->b32[k * 16 + rc];
-        float gold[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) gold[j] = in->g32[(k * 4 + j) * 16 + rc];
-        uint32_t flip = flip_for(SK_F32), n = 0;
-        for (int r = 0; r < p.reps; r++) {
-            sweep_relive(a);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-            n += sweep_count_bad<4>(acc, gold, flip);
-        }
-        bad[SK_F32] = sweep_wave_sum(n);
-    }
-
-    if (p.kinds & (1u << SK_BF16)) {
-        int half = l >> 5, lane32 = l & 31;
-        const __bf16* A = reinterpret_cast<const __bf16*>(in->a16);
-        const __bf16* B = reinterpret_cast<const __bf16*>(in->b16);
-        bf16x8 a, b;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            a[j] = A[lane32 * 16 + half * 8 + j];
-            b[j] = B[(half * 8 + j) * 32 + lane32];
-        }
-        float gold[16];
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++)
-            gold[reg] = in->g16[((reg & 3) + 8 * (reg >> 2) + 4 * half) * 32 + lane32];
-        uint32_t flip = flip_for(SK_BF16), n = 0;
-        for (int r = 0; r < p.reps; r++) {
-            sweep_relive(a);
-            f32x16 acc = {};
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            n += sweep_count_bad<16>(acc, gold, flip);
-        }
-        bad[SK_BF16] = sweep_wave_sum(n);
-    }
-
-    if (p.kinds & (1u << SK_FP8)) {
-        int rc = l & 15, g = l >> 4;
-        uint64_t a = 0, b = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            a |= (uint64_t)in->a8[rc * 32 + 8 * g + j] << (8 * j);
-            b |= (uint64_t)in->b8[(8 * g + j) * 16 + rc] << (8 * j);
-        }
-        float gold[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) gold[j] = in->g8[(g * 4 + j) * 16 + rc];
-        uint32_t flip = flip_for(SK_FP8), n = 0;
-        for (int r = 0; r < p.reps; r++) {
-            sweep_relive(a);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
-            n += sweep_count_bad<4>(acc, gold, flip);
-        }
-        bad[SK_FP8] = sweep_wave_sum(n);
-    }
-
+    if (p.kinds & (1u << SK_F32))
+        bad[SK_F32] = sweep_wave_sum(sweep_form<MfmaF32x16x16x4>(
+            {in->a32, in->b32}, in->g32, l, p.reps, flip_for(SK_F32)));
+    if (p.kinds & (1u << SK_BF16))
+        bad[SK_BF16] = sweep_wave_sum(sweep_form<Mfma32x32x16<__bf16>>(
+            {reinterpret_cast<const __bf16*>(in->a16), reinterpret_cast<const __bf16*>(in->b16)},
+            in->g16, l, p.reps, flip_for(SK_BF16)));
+    if (p.kinds & (1u << SK_FP8))
+        bad[SK_FP8] = sweep_wave_sum(sweep_form<MfmaFp8x16x16x32<FMT_E4M3, FMT_E4M3>>(
+            {in->a8, in->b8}, in->g8, l, p.reps, flip_for(SK_FP8)));
     if (p.kinds & (1u << SK_MX_FP8))
-        bad[SK_MX_FP8] = sweep_wave_sum(sweep_mx<FMT_E4M3>(
-            in->amx8, in->bmx8, in->samx8, in->sbmx8, in->gmx8, l, p.reps,
+        bad[SK_MX_FP8] = sweep_wave_sum(sweep_form<MfmaMx16x16x128<FMT_E4M3, FMT_E4M3>>(
+            {in->amx8, in->bmx8, in->samx8, in->sbmx8}, in->gmx8, l, p.reps,
             flip_for(SK_MX_FP8)));
     if (p.kinds & (1u << SK_MX_FP4))
-        bad[SK_MX_FP4] = sweep_wave_sum(sweep_mx<FMT_E2M1>(
-            in->amx4, in->bmx4, in->samx4, in->sbmx4, in->gmx4, l, p.reps,
+        bad[SK_MX_FP4] = sweep_wave_sum(sweep_form<MfmaMx16x16x128<FMT_E2M1, FMT_E2M1>>(
+            {in->amx4, in->bmx4, in->samx4, in->sbmx4}, in->gmx4, l, p.reps,
             flip_for(SK_MX_FP4)));
 
     if (l == 0) {
@@ -909,11 +727,6 @@ float lcg_f32(uint64_t& s) {
     return f;
 }
 
-uint32_t lcg_bits(uint64_t& s) {
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(s >> 33);
-}
-
 uint16_t bf16_round_bits(float x) {
     // bf16 storage rounding (round-to-nearest-even on the top 16 bits)
     uint32_t u;
@@ -1177,12 +990,6 @@ py::dict mfma_probe_bf16(int dev, int burn_iters) {
 
 // --- FP8 / MX -----------------------------------------------------------------
 
-// A C-contiguous buffer of exactly `count` unsigned bytes.
-const uint8_t* code_buffer(const py::buffer_info& info, size_t count, const char* what) {
-    require(info.format == py::format_descriptor<uint8_t>::format(), what);
-    return (const uint8_t*)tile_buffer(info, 1, count, what);
-}
-
 using fp8_kernel_t = void (*)(const uint8_t*, const uint8_t*, float*);
 using mx_kernel_t = void (*)(const uint8_t*, const uint8_t*, const uint8_t*,
                              const uint8_t*, float*);
@@ -1242,8 +1049,8 @@ py::bytes mfma_fp8_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
     int af = parse_fmt(a_fmt, {FMT_E4M3, FMT_E5M2}, "a_fmt must be 'e4m3' or 'e5m2'");
     int bf = parse_fmt(b_fmt, {FMT_E4M3, FMT_E5M2}, "b_fmt must be 'e4m3' or 'e5m2'");
     py::buffer_info ia = A_codes.request(), ib = B_codes.request();
-    const uint8_t* pa = code_buffer(ia, 512, "A_codes must be 16x32 contiguous uint8");
-    const uint8_t* pb = code_buffer(ib, 512, "B_codes must be 32x16 contiguous uint8");
+    const uint8_t* pa = typed_buffer<uint8_t>(ia, 512, "A_codes must be 16x32 contiguous uint8");
+    const uint8_t* pb = typed_buffer<uint8_t>(ib, 512, "B_codes must be 32x16 contiguous uint8");
     HIP_CHECK(hipSetDevice(dev));
     return as_bytes(run_fp8_tile(pa, pb, af, bf, blocks));
 }
@@ -1260,10 +1067,10 @@ py::bytes mfma_mx_tile_run(int dev, py::buffer A_codes, py::buffer B_codes,
                        "b_fmt must be 'e4m3', 'e5m2' or 'e2m1'");
     py::buffer_info ia = A_codes.request(), ib = B_codes.request();
     py::buffer_info isa = A_scales.request(), isb = B_scales.request();
-    const uint8_t* pa = code_buffer(ia, 2048, "A_codes must be 16x128 contiguous uint8");
-    const uint8_t* pb = code_buffer(ib, 2048, "B_codes must be 128x16 contiguous uint8");
-    const uint8_t* psa = code_buffer(isa, 64, "A_scales must be 16x4 contiguous uint8");
-    const uint8_t* psb = code_buffer(isb, 64, "B_scales must be 4x16 contiguous uint8");
+    const uint8_t* pa = typed_buffer<uint8_t>(ia, 2048, "A_codes must be 16x128 contiguous uint8");
+    const uint8_t* pb = typed_buffer<uint8_t>(ib, 2048, "B_codes must be 128x16 contiguous uint8");
+    const uint8_t* psa = typed_buffer<uint8_t>(isa, 64, "A_scales must be 16x4 contiguous uint8");
+    const uint8_t* psb = typed_buffer<uint8_t>(isb, 64, "B_scales must be 4x16 contiguous uint8");
     for (int i = 0; i < 2048; i++) {
         require(af != FMT_E2M1 || pa[i] < 16, "A_codes: an e2m1 code must be below 16");
         require(bf != FMT_E2M1 || pb[i] < 16, "B_codes: an e2m1 code must be below 16");
@@ -1293,19 +1100,14 @@ py::dict mfma_mx_burn_run(int dev, const std::string& fmt, int iters, int blocks
     return raw_burn(mx_burn_launcher(f), burn_blocks(dev, blocks, 2), iters);
 }
 
-struct LowpTile {
-    bool ok;
-    uint64_t bad_slabs;
-};
-
 // The exact tile of lowp_exact_operands on `blocks` blocks: slab 0 against the
 // host, every other slab against slab 0.
-LowpTile lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
+TileVerdict lowp_exact_tile(int fmt, bool mx, int blocks, uint64_t seed) {
     LowpOperands op = lowp_exact_operands(fmt, mx, seed);
     std::vector<float> hD = mx
         ? run_mx_tile(op.A.data(), op.B.data(), op.SA.data(), op.SB.data(), fmt, fmt, blocks)
         : run_fp8_tile(op.A.data(), op.B.data(), fmt, fmt, blocks);
-    return {std::memcmp(hD.data(), op.ref.data(), 256 * 4) == 0, slab_mismatches(hD, 256)};
+    return judge_tile(hD, op.ref);
 }
 
 // FP8 / MX-FP8 / MX-FP4 matrix-core probe: one fixed exact tile per form on
@@ -1322,9 +1124,9 @@ py::dict mfma_probe_lowp(int dev, int burn_iters) {
     require(burn_iters > 0, "burn_iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    LowpTile fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, LOWP_SEED_FP8);
-    LowpTile mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, LOWP_SEED_MX_FP8);
-    LowpTile mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, LOWP_SEED_MX_FP4);
+    TileVerdict fp8 = lowp_exact_tile(FMT_E4M3, false, blocks, LOWP_SEED_FP8);
+    TileVerdict mx8 = lowp_exact_tile(FMT_E4M3, true, blocks, LOWP_SEED_MX_FP8);
+    TileVerdict mx4 = lowp_exact_tile(FMT_E2M1, true, blocks, LOWP_SEED_MX_FP4);
     int burn_grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
     // FLOPs per block and iteration: 4 waves/WG × accumulators × 2·16·16·128
     const double burn_flops = 4.0 * MX_BURN_ACCS * 2.0 * 16 * 16 * 128;

@@ -17,7 +17,8 @@
 // bitwise against slab 0) and then the two timed burns.
 //
 // Operands arrive row-major and the kernels do the lane packing, so the lane
-// maps below are the ones tests/test_gpu_formats_kernels.py pins on hardware.
+// maps below (f64, i8, sparse) and in mfma_forms.h (f16, and the 16×16 result
+// map) are the ones tests/test_gpu_formats_kernels.py pins on hardware.
 //
 // Wavefront size is 64 (gfx950). Build: hipcc --offload-arch=gfx950, driven by
 // setup.build_hip() next to xpu_probe.hip.
@@ -34,16 +35,10 @@
 #include <string>
 #include <vector>
 
+#include "mfma_forms.h"
 #include "probe_host.h"
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------
 // v_mfma_f64_16x16x4_f64: one f64 of A and B per lane, as the f32 16x16x4
@@ -72,29 +67,13 @@ __global__ void mfma_f64_tile(const double* __restrict__ A,  // 16×4 row-major
 }
 
 // ---------------------------------------------------------------------------
-// v_mfma_f32_32x32x16_f16: the bf16 tile's maps. Lane l (r = l&31, h = l>>5)
-// holds A[r][8h+j] and B[8h+j][r], j = 0..7; C/D col = l&31,
-// row = (reg&3) + 8(reg>>2) + 4h.
+// v_mfma_f32_32x32x16_f16: the bf16 tile's form with the f16 builtin
+// (Mfma32x32x16 in mfma_forms.h).
 // ---------------------------------------------------------------------------
 __global__ void mfma_f16_tile(const _Float16* __restrict__ A,  // 32×16 row-major
                               const _Float16* __restrict__ B,  // 16×32 row-major
                               float* __restrict__ D) {         // gridDim.x × 32×32
-    int l = threadIdx.x & (WAVE - 1);
-    int half = l >> 5, lane32 = l & 31;
-    f16x8 a, b;
-    for (int j = 0; j < 8; j++) {
-        a[j] = A[lane32 * 16 + half * 8 + j];
-        b[j] = B[(half * 8 + j) * 32 + lane32];
-    }
-    f32x16 acc = {};
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-    if (threadIdx.x < WAVE) {
-        float* slab = D + (size_t)blockIdx.x * 1024;
-        for (int reg = 0; reg < 16; reg++) {
-            int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
-            slab[row * 32 + lane32] = acc[reg];
-        }
-    }
+    form_tile<Mfma32x32x16<_Float16>>({A, B}, nullptr, D);
 }
 
 // ---------------------------------------------------------------------------
@@ -132,12 +111,12 @@ __global__ void mfma_i8_tile(const int8_t* __restrict__ A,   // 16×64 row-major
     i32x4 a = pack_i8(va), b = pack_i8(vb);
     i32x4 acc = {0, 0, 0, 0};
     if (C) {
-        for (int r = 0; r < 4; r++) acc[r] = C[(g * 4 + r) * 16 + rc];
+        for (int r = 0; r < 4; r++) acc[r] = C[d_index_16x16(l, r)];
     }
     acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
     if (threadIdx.x < WAVE) {
         int32_t* slab = D + (size_t)blockIdx.x * 256;
-        for (int r = 0; r < 4; r++) slab[(g * 4 + r) * 16 + rc] = acc[r];
+        for (int r = 0; r < 4; r++) slab[d_index_16x16(l, r)] = acc[r];
     }
 }
 
@@ -175,7 +154,7 @@ __global__ void smfmac_f16_tile(const _Float16* __restrict__ A,   // 16×32 kept
     acc = __builtin_amdgcn_smfmac_f32_16x16x64_f16(a, b, acc, (int)idx, 0, 0);
     if (threadIdx.x < WAVE) {
         float* slab = D + (size_t)blockIdx.x * 256;
-        for (int r = 0; r < 4; r++) slab[(q * 4 + r) * 16 + rc] = acc[r];
+        for (int r = 0; r < 4; r++) slab[d_index_16x16(l, r)] = acc[r];
     }
 }
 
@@ -258,14 +237,6 @@ mfma_i8_burn(float* __restrict__ out, int iters) {
 // ---------------------------------------------------------------------------
 // Host-side wrappers
 // ---------------------------------------------------------------------------
-
-// A C-contiguous buffer of exactly `count` items of type T (by format code,
-// so an int8 view is not taken for uint8 nor f32 for i32).
-template <class T>
-const T* typed_buffer(const py::buffer_info& info, size_t count, const char* what) {
-    require(info.format == py::format_descriptor<T>::format(), what);
-    return (const T*)tile_buffer(info, sizeof(T), count, what);
-}
 
 // The tile launches fetch through launch_fetch, which moves 4-byte words: an
 // f64 slab is 512 of them, an i32 slab 256, compared and returned as bytes.
@@ -400,11 +371,6 @@ py::dict mfma_i8_burn_run(int dev, int iters, int blocks) {
 
 // --- probe inputs --------------------------------------------------------------
 
-uint32_t lcg_bits(uint64_t& s) {
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return (uint32_t)(s >> 33);
-}
-
 // A random integer in -range..range.
 int lcg_int(uint64_t& s, int range) { return (int)(lcg_bits(s) % (2 * range + 1)) - range; }
 
@@ -419,25 +385,12 @@ uint16_t f16_bits_of_int(int v) {
     return (uint16_t)(sign | (uint32_t)(e + 15) << 10 | frac);
 }
 
-struct FormatTile {
-    bool ok;
-    uint64_t bad_slabs;
-};
-
-// Slab 0 of `words` against the host's `ref`, every other slab against slab 0.
-template <class T>
-FormatTile judge_tile(const std::vector<float>& words, const std::vector<T>& ref) {
-    size_t slab = ref.size() * sizeof(T) / 4;
-    return {std::memcmp(words.data(), ref.data(), slab * 4) == 0,
-            slab_mismatches(words, slab)};
-}
-
 // f64 exact tile: A and B are integers below 2^24 in magnitude times 2^-1 or
 // 2^0, so a product is a multiple of the step 2^-2 and below 2^48 = 2^50
 // steps; C is such an integer times 2^22, below 2^46. Four products plus C
 // stay below 2^53 steps, so every partial sum is exact in f64 in any order,
 // fused or not, and the comparison is bitwise.
-FormatTile f64_exact_tile(int blocks) {
+TileVerdict f64_exact_tile(int blocks) {
     uint64_t rng = 0xBE5466CF34E90C6Cull;
     std::vector<double> A(64), B(64), C(256), ref(256);
     auto draw = [&] {
@@ -458,7 +411,7 @@ FormatTile f64_exact_tile(int blocks) {
 
 // f16 exact tile: integer-valued f16 in -16..16. A product is at most 256 and
 // 16 of them sum to at most 4096: every partial sum is an integer below 2^24.
-FormatTile f16_exact_tile(int blocks) {
+TileVerdict f16_exact_tile(int blocks) {
     uint64_t rng = 0xC0AC29B7C97C50DDull;
     std::vector<int> a(512), b(512);
     std::vector<uint16_t> A(512), B(512);
@@ -476,7 +429,7 @@ FormatTile f16_exact_tile(int blocks) {
 
 // i8 exact tile: full-range int8 and a C of up to ±2^30; |Σ| ≤ 64·2^14 = 2^20,
 // so nothing wraps.
-FormatTile i8_exact_tile(int blocks) {
+TileVerdict i8_exact_tile(int blocks) {
     uint64_t rng = 0x3F84D5B5B5470917ull;
     std::vector<int8_t> A(1024), B(1024);
     std::vector<int32_t> C(256), ref(256);
@@ -497,7 +450,7 @@ FormatTile i8_exact_tile(int blocks) {
 // number (i + g) % 6 of (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), so all six occur
 // in every row and every group column. 32 products of at most 256: integers
 // below 2^24 under any order.
-FormatTile sparse_exact_tile(int blocks) {
+TileVerdict sparse_exact_tile(int blocks) {
     static const uint8_t PAIRS[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
     uint64_t rng = 0x9216D5D98979FB1Bull;
     std::vector<int> a(512), b(1024);
@@ -530,10 +483,10 @@ py::dict mfma_probe_formats(int dev, int burn_iters) {
     require(burn_iters > 0, "burn_iters must be > 0");
     HIP_CHECK(hipSetDevice(dev));
     int blocks = std::min(compute_units(dev) * 2, MAX_TILE_BLOCKS);
-    FormatTile f64 = f64_exact_tile(blocks);
-    FormatTile f16 = f16_exact_tile(blocks);
-    FormatTile i8 = i8_exact_tile(blocks);
-    FormatTile sp = sparse_exact_tile(blocks);
+    TileVerdict f64 = f64_exact_tile(blocks);
+    TileVerdict f16 = f16_exact_tile(blocks);
+    TileVerdict i8 = i8_exact_tile(blocks);
+    TileVerdict sp = sparse_exact_tile(blocks);
     int burn_grid = burn_blocks(dev, 0, 2);   // 2 × 256-thread WGs per CU
     // operations per block and iteration: 4 waves/WG × accumulators × 2·M·N·K
     TimedBurn b64 = timed_burn(launch_f64_burn, burn_grid, burn_iters,

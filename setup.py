@@ -20,8 +20,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = "kata_xpu_device_plugin_amd"
 
 
-# HIP extension module → its source under probes/. Both include
-# probes/probe_host.h.
+# HIP extension module → its source under probes/. Both include the headers
+# there (probes/*.h: probe_host.h, mfma_forms.h).
 HIP_EXTENSIONS = {
     "_gpuprobe": "xpu_probe.hip",
     "_gpuprobe_formats": "xpu_probe_formats.hip",
@@ -32,17 +32,18 @@ def build_hip(arch: str = "gfx950", verbose: bool = True) -> str:
     """Compile probes/xpu_probe.hip → kata_xpu_device_plugin_amd/_gpuprobe.so
     and probes/xpu_probe_formats.hip → …/_gpuprobe_formats.so with the same
     flags; returns the _gpuprobe path. An output newer than its source and
-    the shared header is kept."""
+    every header under probes/ is kept."""
+    import glob
     import sysconfig
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    header = os.path.join(ROOT, "probes", "probe_host.h")
+    headers = glob.glob(os.path.join(ROOT, "probes", "*.h"))
     ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     outs = {}
     for mod, name in HIP_EXTENSIONS.items():
         src = os.path.join(ROOT, "probes", name)
         out = outs[mod] = os.path.join(ROOT, PKG, f"{mod}{ext}")
-        newest = max(os.path.getmtime(src), os.path.getmtime(header))
+        newest = max(os.path.getmtime(p) for p in [src, *headers])
         if os.path.exists(out) and os.path.getmtime(out) > newest:
             continue
         cmd = [

@@ -87,7 +87,7 @@ def pick_unit(covered):
     return xcd, key, placement.decode(r[0], r[1]).simd
 
 
-@pytest.mark.parametrize("kind", ["bf16", "mx_fp4"])
+@pytest.mark.parametrize("kind", ["f32", "bf16", "fp8", "mx_fp8", "mx_fp4"])
 def test_poisoned_matrix_unit_is_named(gp, covered, cus, kind):
     xcd, key, simd = pick_unit(covered)
     res = gp.unit_sweep_run(0, ALL, 8, poison=(xcd, key, simd, kind, FLIP))
